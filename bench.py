@@ -21,7 +21,9 @@ N > 1 : strong scaling of the SAME graph with the full C on every rank at the en
 
 Launch: python bench.py --gpus N --steps 20 --warmup 5          (N > 1 without WORLD_SIZE: starts its own N ranks as children)
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline; --full adds the
+measurements and checks beside it (CPU baseline, oracle checks, BASELINE's other configurations, ...).  --dump-outputs DIR
+writes C of the last timed step.
 """
 import argparse
 import json
@@ -138,6 +140,17 @@ def self_launch(n_gpus):
     return _launch(os.path.abspath(__file__), n_gpus, sys.argv[1:], threads_per_rank=max(1, cpu_quota() // max(n_gpus, 1)), tag="bench")
 
 
+def dump_outputs(out_dir, c, n, h):
+    """--dump-outputs: the [n, h] float32 C a caller of the timed step receives, as out_dir/c.npy.  Above 48 MiB a fixed sample of
+    rows (numpy default_rng(0), ascending): the inputs are seeded, so the same arguments give the same rows on any build."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(1, (48 << 20) // (4 * h))
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    got = c.index_select(0, torch.from_numpy(rows).to(c.device)).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "c.npy"), got)
+    print(f"[bench] wrote {os.path.join(out_dir, 'c.npy')}: {got.shape[0]} of {n} rows x {h} features of C", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,7 +166,16 @@ def main():
     ap.add_argument("--partition", default="auto", choices=["auto", "row", "feature", "pipelined", "pipelined-feature", "push", "push-feature"])
     ap.add_argument("--chunks", type=int, default=0, help="row pieces per rank (0 = 1 on one GPU; on N > 1 the fastest of 1 / 2 / 4, measured before the warm-up)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what lies beside the headline: the CPU baseline and the oracle checks, BASELINE's other "
+                         "configurations, the structured-graph extras, the creation-cost alternatives and, on N > 1, the products-only "
+                         "step and the checksum of the gathered C (--no-cpu-baseline / --no-check / --no-extra trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write C of the last timed step to DIR/c.npy (float32): every row when they fit in 48 MiB, else a fixed "
+                         "seeded sample of rows in ascending order")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -452,9 +474,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan.full_c(), n, h)   # before anything below runs a product into the same buffers
     # for reading the scaling: the same step without the exchange (each rank's products only), outside the timed region
     products_only_ms = None
-    if multi:
+    if multi and args.full:
         fence()
         t1 = time.perf_counter()
         for _ in range(3):
@@ -588,7 +612,7 @@ def main():
     }
 
     e2e_host = None
-    if rank == 0 and world == 1 and not args.clustered and not args.no_extra and (args.shape, h) == ("reddit", 256):
+    if args.full and rank == 0 and world == 1 and not args.clustered and not args.no_extra and (args.shape, h) == ("reddit", 256):
         # the reference driver's default call (CPU tensors in and out), FIRST among the extras: what spmm_test.py does is this call in a process that has done
         # little else, and the DMA engines the runtime hands the call's copy streams depend on what the process did before (profiles/r06_exp_host_call.txt:
         # 8.2 ms in a fresh process; after the BASELINE-config legs below the pitched downloads run at 21 GB/s and the group turns to direct stores: 9.0)
@@ -598,7 +622,7 @@ def main():
             e2e_host = _bc.end_to_end_cpu_tensors(rowptr, col, n, h)
         except Exception as e:  # noqa: BLE001  (an extra: never the reason the line is missing)
             e2e_host = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
-    if rank == 0 and world == 1 and not args.clustered and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.clustered and not args.no_extra:
         # SURVEY.md 8(d) asks for both column shapes: the same product on the community-like variant of the graph (columns within
         # ~1 % of the row id), measured here OUTSIDE the timed region and reported beside the headline
         rp_c, col_c = synth.make_csr(n, nnz, d_max, seed=0, device=dev, clustered=True)
@@ -753,7 +777,7 @@ def main():
                 if hy_prev is not None:
                     _lib.set_tunable("lds_hybrid", hy_prev)
                 result["extra"]["products_sbm_shuffled_ids"] = {"error": str(e)[:160]}
-    if rank == 0 and world == 1 and not args.no_extra and not args.clustered and (args.shape, h) == ("reddit", 256):
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.clustered and (args.shape, h) == ("reddit", 256):
         # BASELINE.json's OTHER configurations beside the headline, each with its own roofline object and check, measured
         # outside the timed region (pygim_amd/bench_configs.py); the SBM / clustered extras above are graphs of this build's own making
         from pygim_amd import bench_configs
@@ -781,7 +805,7 @@ def main():
                 result["extra"]["end_to_end_cpu_tensors"]["after_the_other_legs"] = {k: again[k] for k in ("ms_per_mul", "direct_stores", "ms_each_call", "ms_per_mul_serial", "check") if k in again}
             except Exception as e:  # noqa: BLE001
                 result["extra"]["end_to_end_cpu_tensors"]["after_the_other_legs"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, cpu_out = cpu_baseline(rowptr, col, x, args)
         result["cpu_baseline"] = base
         if not args.no_check:
@@ -817,7 +841,7 @@ def main():
                     "bar": "1e-5 relative (BASELINE.json north_star); |A||x| is the backward-stable scale of a 500-term sum"}
                 if result["check_uniform_f32"]["max_err_rel_absAx"] > 1e-5:
                     result["check"] = "MISMATCH"
-    if multi:
+    if multi and args.full:
         # every rank now holds every block: column-count checksum of the assembled C (exact: small integers)
         full = plan.full_c()
         colcount = torch.bincount(col.long(), minlength=n).double()

@@ -8,7 +8,7 @@ LIMIT=${3:-1700}     # seconds per launch (8 ranks that share ONE GPU can starve
 mkdir -p gpurun_out/multirank
 for part in auto row feature pipelined pipelined-feature; do
   t0=$(date +%s)
-  PYGIM_BENCH_BACKEND=gloo PYGIM_RANK_TIMEOUT=$((LIMIT - 60)) PYGIM_COLLECTIVE_TIMEOUT=$((LIMIT - 120)) PYGIM_LAUNCH_TIMEOUT=$LIMIT timeout $((LIMIT + 30)) python bench.py --gpus $R --steps 3 --warmup 1 --shape $SHAPE --partition $part \
+  PYGIM_BENCH_BACKEND=gloo PYGIM_RANK_TIMEOUT=$((LIMIT - 60)) PYGIM_COLLECTIVE_TIMEOUT=$((LIMIT - 120)) PYGIM_LAUNCH_TIMEOUT=$LIMIT timeout $((LIMIT + 30)) python bench.py --gpus $R --steps 3 --warmup 1 --shape $SHAPE --partition $part --full \
       > gpurun_out/multirank/n${R}_${SHAPE}_${part}.json 2> gpurun_out/multirank/n${R}_${SHAPE}_${part}.err
   rc=$?
   echo "ranks=$R shape=$SHAPE partition=$part rc=$rc seconds=$(( $(date +%s) - t0 ))"

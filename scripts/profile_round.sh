@@ -13,6 +13,6 @@ cp $out/traffic.json profiles/traffic_latest.json 2>/dev/null
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --no-extra > $out/bench_under_rocprof.log 2>&1
 cd $R
-python3 bench.py > $out/bench_n1.json 2> $out/bench_n1.err
+python3 bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
 tail -1 $out/bench_n1.json | cut -c1-400
 find $out -name "*kernel_stats.csv" | head -2

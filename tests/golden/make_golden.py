@@ -17,6 +17,9 @@ Sources of truth, in order:
   * group_*.npz      -- sp_parts x ds_parts group products from the reference's own group drivers
                         (spmm_host_csr_group / spmm_host_coo_group, spmm_default/ops.hpp:42-62,
                         97-118) on the reference's own structs (oracle/ref_host_glue.inc).
+  * ref_digests.json -- sha256 of the reference build's results in tests/test_oracle.py's reference tests (RefOutputs): what those
+                        tests compare with where oracle/_ref is not built.  Rewritten, with oracle/_ref built, by
+                        PYGIM_RECORD_REF_DIGESTS=1 python -m pytest tests/test_oracle.py
 Inputs follow the reference driver: graph shapes of SURVEY.md section 8c, features
 torch.randint(-8, 4) under torch.manual_seed (spmm_test.py:70).
 Usage: python tests/golden/make_golden.py [quant]

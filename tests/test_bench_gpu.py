@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_emits_one_json_line_with_the_contract_fields():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--cpu-rows", "4096"], capture_output=True, text=True, timeout=600)
+                        "--cpu-rows", "4096", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -54,6 +54,32 @@ def test_bench_emits_one_json_line_with_the_contract_fields():
     assert c5["feature_split_1x8"]["h"] == 16 and c5["grid_2x4"]["h"] == 32 and c4["aggregations_per_forward"] == 3
     assert d["extra"]["end_to_end_cpu_tensors_ms"] > d["ms_per_step"] and "MISMATCH" not in d["extra"]["end_to_end_cpu_tensors"]["check"]
     assert "NOT BASELINE" in d["extra"]["note_on_structured_graphs"]
+
+
+def test_plain_run_prints_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """without --full the line holds the headline and what its timed steps measured, nothing measured beside them;
+    --dump-outputs writes C of the last timed step (a small shape: every row), equal to the oracle's product of the same seeded inputs"""
+    import torch
+
+    import oracle
+    from pygim_amd import synth
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--shape", "products-mini",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["metric"].startswith("SpMM GFLOP/s")
+    for k in ("cpu_baseline", "check", "check_uniform_f32", "extra", "extra_headline", "baseline_configs"):
+        assert k not in d, k
+    n, nnz, d_max = synth.SHAPES["products-mini"]
+    c = np.load(tmp_path / "c.npy")
+    assert c.dtype == np.float32 and c.shape == (n, 256)
+    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device="cuda")
+    x = synth.features(n, 256, torch.float32, seed=0, device="cuda")
+    assert np.array_equal(c, oracle.spmm_csr(rowptr.cpu().numpy(), col.cpu().numpy(), None, x.cpu().numpy()))
 
 
 def _parse_like_the_harness(stdout):
@@ -142,7 +168,7 @@ def test_bench_two_ranks_logic_check(partition):
     env = dict(os.environ, PYGIM_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr=127.0.0.1",
            f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--shape", "products-mini",
-           "--partition", partition]
+           "--partition", partition, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -158,7 +184,7 @@ def test_bench_launches_its_own_ranks_as_a_plain_command():
     gloo on this one GPU: a logic check, not a measurement).  A rank that fails must make the command fail."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PYGIM_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--shape", "products-mini"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--shape", "products-mini", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -178,7 +204,7 @@ def test_a_rank_that_fails_in_set_up_ends_every_rank_promptly():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PYGIM_BENCH_BACKEND="gloo", PYGIM_RANK_TIMEOUT="600", PYGIM_COLLECTIVE_TIMEOUT="300")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--shape", "products-mini"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--shape", "products-mini", "--full"]
     for part in ("auto", "row", "pipelined"):
         t0 = time.time()
         bad = subprocess.run(cmd + ["--partition", part], capture_output=True, text=True, timeout=900, env={**env, "PYGIM_BENCH_FAIL_RANK": "1"}, cwd=ROOT)
@@ -200,7 +226,8 @@ def test_bench_eight_ranks_logic_check():
     Reddit shape eight processes on one GPU starve one another for minutes -- profiles/r04_multirank.txt -- so the small shape here.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PYGIM_BENCH_BACKEND="gloo", PYGIM_RANK_TIMEOUT="500", PYGIM_COLLECTIVE_TIMEOUT="400", PYGIM_LAUNCH_TIMEOUT="560")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--shape", "products-mini", "--partition", "pipelined"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--shape", "products-mini", "--partition", "pipelined",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -105,3 +105,25 @@ def test_bench_arrangements_over_gloo(world):
     for p in procs:
         p.join(30)
     assert all(r[1] == "ok" for r in res), res
+
+
+def test_dump_outputs_samples_a_fixed_set_of_rows_within_the_cap(tmp_path):
+    """bench.py --dump-outputs on an output above its 48 MiB cap: the same seeded rows, ascending and distinct, every feature of them,
+    float32 -- so that two builds' files compare element for element"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    n, h = 70000, 256
+    c = torch.zeros((n, h), dtype=torch.float32)
+    c[:, 0] = torch.arange(n, dtype=torch.float32)
+    c[:, h - 1] = 1.0
+    got = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), c, n, h)
+        got.append(np.load(tmp_path / run / "c.npy"))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == ((48 << 20) // (4 * h), h) and a.nbytes <= 64 << 20
+    rows = a[:, 0].astype(np.int64)
+    assert np.array_equal(a, b) and np.all(np.diff(rows) > 0) and rows[-1] < n and np.all(a[:, h - 1] == 1.0)

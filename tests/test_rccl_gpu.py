@@ -43,7 +43,7 @@ def test_bench_one_rank_over_rccl(partition):
     """every exchange scheme of bench.py with its collectives running on RCCL: the gathered C is exact, the JSON line says
     how many ranks RCCL saw and which candidate ran"""
     d = _bench_line(_torchrun("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--partition", partition,
-                                           "--chunks", "2" if partition in ("row", "feature") else "0", "--no-cpu-baseline"]))
+                                           "--chunks", "2" if partition in ("row", "feature") else "0", "--no-cpu-baseline", "--full"]))
     assert d["n_gpus"] == 1 and d["config"]["rccl_world"] == 1 and d["config"]["backend"] == "nccl"
     assert d["check"].startswith("column-count checksum"), d.get("check")
     assert d["config"]["ms_per_step_products_only"] > 0
@@ -62,7 +62,7 @@ def test_bench_torchrun_number_equals_plain_number():
         return _bench_line(r.stdout)
 
     before = plain_run()
-    t = _bench_line(_torchrun("bench.py", ["--gpus", "1", "--steps", "30", "--warmup", "10", "--no-cpu-baseline"]))
+    t = _bench_line(_torchrun("bench.py", ["--gpus", "1", "--steps", "30", "--warmup", "10", "--no-cpu-baseline", "--full"]))
     after = plain_run()
     prod = t["config"]["ms_per_step_products_only"]
     p = min((before, after), key=lambda d: abs(d["ms_per_step"] - prod))

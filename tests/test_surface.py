@@ -24,7 +24,11 @@ TORCH_OF = {"INT8": torch.int8, "INT16": torch.int16, "INT32": torch.int32, "INT
 def fake(monkeypatch):
     f = FakeLib()
     monkeypatch.setattr(pim_ops, "_lib", f)
-    monkeypatch.setattr(pim_ops, "_variant", None)
+    # the wrappers' paths of a machine without a GPU, wherever the suite runs (with one, spmv's mul takes the real library's device path)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    # not monkeypatched: the registration a GPU test left behind is replaced below, so restoring its variant name would leave
+    # pim_ops claiming a variant whose ops are gone; the next load() registers afresh
+    pim_ops._variant = None
     yield f
     if pim_ops._library is not None:
         assert pim_ops._library != "native", "a test loaded the C++ shim in the pytest process"
