@@ -116,6 +116,20 @@ int pygim_group_create(int format, int dtype, int n_parts,
                        int64_t h_size, int64_t *out_handle);
 /* Replaces spmm_free_group (spmm_default/pytorch_api.cpp:198-201). */
 int pygim_group_free(int64_t handle);
+/* The group of A^T, for the backward product dX = A^T . G of an aggregation: exactly pygim_group_create's arguments,
+ * where A is the matrix they describe (the column blocks side by side, nrows[0] x sum(ncols)).  The input is validated
+ * with the same checks and error codes, host arrays are uploaded once and device arrays read in place (they need not
+ * outlive the call), and the transpose runs on the device.  Row c of A^T lists the entries of global column c in the
+ * order they have in A: ascending row, stored order among duplicates (a stable sort by column, torch_sparse's t());
+ * part i's columns become the rows from sum_{j<i} ncols[j] on.  The result is an ordinary group -- one CSR sparse part of
+ * sum(ncols) x nrows[0], the same dtype and h_size, one dense part of width h_size -- built by the same creation path
+ * (unit weights, plans, code streams and fallbacks as for any group) with its own serial; pygim_group_free or
+ * pygim_release frees it.  All six types, CSR or COO input.                                                          */
+int pygim_group_create_transposed(int format, int dtype, int n_parts,
+                                  const int32_t *const *idx0, const int32_t *const *colind,
+                                  const void *const *values, const int64_t *nrows, const int64_t *ncols,
+                                  const int64_t *nnz, const int64_t *n_dense, const int64_t *dense_cols,
+                                  int64_t h_size, int64_t *out_handle);
 
 /* ---- run -----------------------------------------------------------------
  * pygim_spmm_run_group replaces spmm_csr_run_group / spmm_coo_run_group
@@ -185,6 +199,16 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
 /* the last two of those steps in one sweep: out = float(A . Xq) * scale, Xq [total_cols, h] already quantised in the
  * group's type (row stride ldx), the dequantisation done by the sweep's last store per row (no integer result matrix). */
 int pygim_spmm_run_dequant(int64_t handle, const void *Xq, int64_t ldx, float *out, const uint32_t *absmax_bits, void *stream);
+
+/* ---- sampled dense-dense product (the gradient of an aggregation with respect to the edge values) ----
+ *   out[e] = sum_f G[row(e), f] * X[colind[e], f]   for every stored entry e of the CSR (rowptr: nrows + 1, colind: nnz),
+ * in stored order.  G: [nrows, h] with row stride ldg, X: [max column + 1, h] with row stride ldx, out: nnz elements; any
+ * h >= 1, nnz = 0 and empty rows allowed.  FLT32 and DBL64 only (else PYGIM_ERR_INVALID); device pointers only, the
+ * caller guarantees a valid CSR (rowptr non-decreasing from 0 to nnz, column ids inside X).  Every entry owns its output:
+ * no atomics, the same bits on every run; each sum is a fixed-order sum over the features (within 1e-5 (FLT32) /
+ * 1e-12 (DBL64) of sum_f |G . X| of the exact value).  Only enqueues work on `stream`.                                */
+int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *G,
+                int64_t ldg, const void *X, int64_t ldx, int64_t h, void *out, void *stream);
 
 /* ---- introspection -----------------------------------------------------------
  * Milliseconds of the last host-pointer run, in the reference's Timer buckets

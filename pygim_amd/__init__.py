@@ -8,5 +8,8 @@ Layout:
   sparse_tensor.py stand-in for torch_sparse.SparseTensor when that package is absent
   synth.py         seeded synthetic graphs in the shapes BASELINE.json names
   dist.py          sp_parts / ds_parts across the GPUs of one node (torch.distributed/RCCL)
+  autograd.py      gradients of ``mul``: A^T . G through a transposed group, the edge values' SDDMM (``sddmm``)
 """
 __version__ = "0.1.0"
+
+from .autograd import sddmm  # noqa: E402,F401

@@ -20,6 +20,7 @@ EXPORTS = [
     "pygim_group_kernel_events", "pygim_group_plan", "pygim_spmm_run_dequant",
     "pygim_quant_spmm_run_post", "pygim_generation", "pygim_group_lds_plan", "pygim_group_lds_code", "pygim_group_lds_geometry", "pygim_group_lds_note",
     "pygim_group_lds_tiles", "pygim_group_lds_runs", "pygim_group_serial", "pygim_group_host_windows",
+    "pygim_group_create_transposed", "pygim_sddmm",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -58,6 +59,8 @@ def lib():
         L.pygim_device_info.argtypes = [ctypes.c_char_p, c_int, ctypes.POINTER(c_int), p_i64]
         L.pygim_group_create.argtypes = [c_int, c_int, c_int, vp, vp, vp, p_i64, p_i64, p_i64, p_i64, p_i64, c_i64,
                                          p_i64]
+        L.pygim_group_create_transposed.argtypes = list(L.pygim_group_create.argtypes)
+        L.pygim_sddmm.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, vp, vp]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -151,6 +154,24 @@ def group_create(fmt, dtype, idx0_ptrs, col_ptrs, val_ptrs, nrows, ncols, nnz, n
                                    i64_array(ncols), i64_array(nnz), i64_array(n_dense), i64_array(dense_cols),
                                    int(h), ctypes.byref(handle)))
     return handle.value
+
+
+def group_create_transposed(fmt, dtype, idx0_ptrs, col_ptrs, val_ptrs, nrows, ncols, nnz, n_dense, dense_cols, h):
+    """the group of A^T for the arguments that describe A (include/pygim_hip.h): one CSR part of sum(ncols) x nrows[0]"""
+    n = len(col_ptrs)
+    handle = ctypes.c_int64(0)
+    vals = None if val_ptrs is None else ptr_array(val_ptrs)
+    check(lib().pygim_group_create_transposed(fmt, dtype, n, ptr_array(idx0_ptrs), ptr_array(col_ptrs), vals, i64_array(nrows),
+                                              i64_array(ncols), i64_array(nnz), i64_array(n_dense), i64_array(dense_cols),
+                                              int(h), ctypes.byref(handle)))
+    return handle.value
+
+
+def sddmm(dtype, nrows, rowptr_ptr, col_ptr, nnz, g_ptr, ldg, x_ptr, ldx, h, out_ptr, stream=0):
+    """out[e] = G[row(e)] . X[col[e]] for every stored entry of a CSR (device pointers; FLT32 / DBL64)"""
+    check(lib().pygim_sddmm(int(dtype), int(nrows), ctypes.c_void_p(rowptr_ptr or None), ctypes.c_void_p(col_ptr or None), int(nnz),
+                            ctypes.c_void_p(g_ptr or None), int(ldg), ctypes.c_void_p(x_ptr or None), int(ldx), int(h),
+                            ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 def group_free(handle):

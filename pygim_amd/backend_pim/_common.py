@@ -57,6 +57,7 @@ class SparseGroupBase:
         self.dtype = dtype
         self.format = format
         self._handle = None  # (handle, generation) of the device group this object owns
+        self._handle_t = None  # (handle, serial, h) of the group of A^T (mul_t), made on the first backward
         self.sp_info_ptr = None
         self.result = None
         self.parts = [self.raw]
@@ -88,9 +89,10 @@ class SparseGroupBase:
                 self._handle = (int(handle), None)
 
     def free_group(self):
-        """spmm_free_group on the group this object created, if it is still alive."""
+        """spmm_free_group on the group this object created, if it is still alive (and on its A^T group, see mul_t)."""
         from .. import _lib
 
+        self._free_transposed()
         held, self._handle = getattr(self, "_handle", None), None
         if held is None or held[1] is None or not _lib.is_initialized():
             return
@@ -106,6 +108,83 @@ class SparseGroupBase:
             self.free_group()
         except Exception:  # interpreter shutdown: torch.ops or the library may be gone already
             pass
+
+    # -- the backward product: A^T . G (pygim_amd/autograd.py) ------------------------------------------
+    # A second device group, of A^T, built from the same per-part arrays the wrapper handed to *_to_device_group (self.csr /
+    # self.coo) and transposed on the device (pygim_group_create_transposed).  It is a compiled group like the forward's: on a
+    # Reddit-like graph about 1 GB of code plus the transient memory of creation (README: about 1.0 GB and 5 GB for the forward
+    # group), paid on the first backward -- or up front with prepare_backward() -- and never by a model that only runs forward.
+    # Owned like the forward group: freed by free_group, by to_pim_group* and when the object dies, guarded by its serial.
+    def _free_transposed(self):
+        from .. import pim_ops
+
+        held, self._handle_t = getattr(self, "_handle_t", None), None
+        if held is None:
+            return
+        L = pim_ops._lib
+        if not L.is_initialized():
+            return
+        try:
+            alive = L.group_serial(held[0]) == held[1]
+        except L.PygimError:  # freed by dpu_release
+            alive = False
+        if alive:
+            L.group_free(held[0])
+
+    def _group_arrays(self):
+        """(format code, idx0, col, values, nrows, ncols) per part: what to_pim_group* passed to the library"""
+        from .. import _lib
+
+        if self.format == "CSR":
+            return (_lib.CSR, [p.crow_indices() for p in self.csr], [p.col_indices() for p in self.csr],
+                    [p.values() for p in self.csr], [p.size(0) for p in self.csr], [p.size(1) for p in self.csr])
+        if self.format == "COO":
+            return (_lib.COO, self.row_indices, self.col_indices, self.values, [c.size(0) for c in self.coo],
+                    [c.size(1) for c in self.coo])
+        raise RuntimeError("mul_t: no device group (call to_pim_group first)")
+
+    def _transposed(self, h):
+        """handle of the A^T group for h features (made here on first use)"""
+        from .. import pim_ops
+
+        L = pim_ops._lib
+        held = self._handle_t
+        if held is not None:
+            try:
+                if held[2] == h and L.group_serial(held[0]) == held[1]:
+                    return held[0]
+            except L.PygimError:  # freed by dpu_release: build again
+                self._handle_t = None
+        self._free_transposed()
+        fmt, idx0, cols, vals, nrows, ncols = self._group_arrays()
+        n = len(cols)
+        handle = L.group_create_transposed(fmt, pim_ops.DTYPE_CODE[self.dtype], [t.data_ptr() for t in idx0], [t.data_ptr() for t in cols],
+                                           [v.contiguous().data_ptr() for v in vals], nrows, ncols, [v.numel() for v in vals], [1] * n,
+                                           [int(h)] * n, int(h))
+        self._handle_t = (handle, L.group_serial(handle), int(h))
+        return handle
+
+    def prepare_backward(self, h=None):
+        """build the A^T group now instead of on the first backward (h: feature width of the gradients, default hidden_size)"""
+        self._transposed(int(h if h is not None else self.hidden_size))
+
+    def mul_t(self, G: torch.Tensor):
+        """A^T . G for every dtype: G [rows of A, h] (CPU or device tensor, the group's dtype), result [columns of A, h] on G's
+        device, like mul.  The gradient of ``mul`` with respect to its dense operand."""
+        from .. import pim_ops
+
+        assert G.dim() == 2 and G.dtype == self.dtype, "mul_t: G must be [rows, h] in the group's dtype"
+        fmt, idx0, cols, vals, nrows, ncols = self._group_arrays()
+        rows, total_cols = int(nrows[0]), int(sum(ncols))
+        if G.size(0) < rows:  # (spmv pads the matrix: padded rows have no gradient)
+            G = torch.nn.functional.pad(G, (0, 0, 0, rows - G.size(0)))
+        assert G.size(0) == rows, "mul_t: G has more rows than A"
+        G = G.contiguous()
+        h = G.size(1)
+        handle = self._transposed(h)
+        out = pim_ops._new_out((total_cols, h), self.dtype, G.device)
+        pim_ops._lib.spmm_run_group(handle, [G.data_ptr()], out.data_ptr(), pim_ops._stream_of(out))
+        return out[:self.raw.size(1)] if total_cols != self.raw.size(1) else out
 
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):

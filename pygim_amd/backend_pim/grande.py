@@ -7,6 +7,7 @@ an XCD-sized feature window of the same launch (``dpu_init_ranks`` reports 8 per
 """
 import torch
 
+from .. import autograd
 from ._common import TORCH_TYPES, SparseGroupBase  # noqa: F401
 
 # elements per 8 bytes (grande.py:11)
@@ -54,6 +55,12 @@ class SparseTensorCOO(SparseGroupBase):
             self.dense_ncols, hidden_size)
 
     def mul(self, B: torch.Tensor):
+        """A . B; differentiable in B when a gradient is wanted (pygim_amd/autograd.py; the values were cut off by coo.int())"""
+        if autograd.wants_grad(self, B, None):
+            return autograd.aggregate(self, B)
+        return self._mul(B)
+
+    def _mul(self, B: torch.Tensor):
         assert self.hidden_size == B.size(1)
         assert len(self.dpus_per_rank) == len(self.csr)
         row_blocks = torch.split(B, [p.size(1) for p in self.csr], dim=0)

@@ -9,6 +9,7 @@ by side (spmm.py:57-122).  The arithmetic runs in the HIP library behind
 """
 import torch
 
+from .. import autograd
 from ._common import TORCH_TYPES, SparseGroupBase, split_widths  # noqa: F401 (TORCH_TYPES re-exported)
 
 
@@ -54,6 +55,13 @@ class SparseTensorCOO(SparseGroupBase):
             assert False
 
     def mul(self, B: torch.Tensor):
+        """A . B; differentiable in B and in the raw tensor's value when a gradient is wanted (pygim_amd/autograd.py)"""
+        value = self.raw.storage.value()
+        if autograd.wants_grad(self, B, value):
+            return autograd.aggregate(self, B, value if value is not None and value.requires_grad else None)
+        return self._mul(B)
+
+    def _mul(self, B: torch.Tensor):
         assert self.hidden_size == B.size(1)
         blocks = dense_split(B, self.dense_parts)
         if self.format == "CSR":

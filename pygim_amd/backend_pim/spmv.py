@@ -1,12 +1,14 @@
 """SparseP-style SpMV wrapper -- same public surface as the reference's backend_pim/spmv.py.
 
 An SpMM with h features runs as h SpMVs, ``groups`` (= ds_parts) vectors per backend
-call (spmv.py:89-102).  Integer dtypes only (``torch.iinfo``, spmv.py:45); the matrix is
+call (spmv.py:89-102).  The reference takes integer dtypes only (``torch.iinfo``, spmv.py:45); float groups are
+accepted here too (``torch.finfo``), so that ``mul`` can be trained through (pygim_amd/autograd.py).  The matrix is
 padded to a multiple of 64/bits rows and columns (spmv.py:45-51) and results are cut
 back to the true row count (spmv.py:93).
 """
 import torch
 
+from .. import autograd
 from ._common import TORCH_TYPES, SparseGroupBase, split_widths  # noqa: F401
 
 
@@ -39,7 +41,7 @@ class SparseTensorCOO(SparseGroupBase):
         super().__del__()
 
     def build_coo(self):
-        quantum = 64 // torch.iinfo(self.dtype).bits
+        quantum = 64 // (torch.finfo if self.dtype.is_floating_point else torch.iinfo)(self.dtype).bits
         self.coo = []
         for item in self.parts:
             extra = (-item.size(0)) % quantum
@@ -75,6 +77,12 @@ class SparseTensorCOO(SparseGroupBase):
         return res[:self.raw.size(0), ...]
 
     def mul(self, B: torch.Tensor):
+        """A . B; differentiable in B when a gradient is wanted (pygim_amd/autograd.py; the values were cut off by coo.int())"""
+        if autograd.wants_grad(self, B, None):
+            return autograd.aggregate(self, B)
+        return self._mul(B)
+
+    def _mul(self, B: torch.Tensor):
         if B.dtype == self.dtype and len(self.coo) == 1 and B.dim() == 2 and B.size(1) % self.groups == 0:
             if B.is_cuda:
                 return self._mul_device(B)

@@ -21,6 +21,8 @@
 #include "lds_reorder_dev.hpp"
 #include "lds_hybrid_dev.hpp"
 #endif
+#include "transpose_dev.hpp"
+#include "sddmm_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -206,11 +208,22 @@ int64_t pygim_set_tunable(const char *name, int64_t value) {
     return old;
 }
 
-int pygim_group_create(int format, int dtype, int n_parts, const int32_t *const *idx0,
-                       const int32_t *const *colind, const void *const *values, const int64_t *nrows,
-                       const int64_t *ncols, const int64_t *nnz, const int64_t *n_dense,
-                       const int64_t *dense_cols, int64_t h_size, int64_t *out_handle) {
-    if (int rc = need_init()) return rc;
+}  // extern "C"
+
+// The body of pygim_group_create.  adopt: the (device) arrays of the single part were allocated by the library for this group
+// (pygim_group_create_transposed) -- the group owns them from creation on, and they are freed here when creation fails.
+static int group_create(int format, int dtype, int n_parts, const int32_t *const *idx0, const int32_t *const *colind,
+                        const void *const *values, const int64_t *nrows, const int64_t *ncols, const int64_t *nnz,
+                        const int64_t *n_dense, const int64_t *dense_cols, int64_t h_size, int64_t *out_handle, bool adopt) {
+    bool adopted = false;
+    auto drop_adopted = [&]() {
+        if (!adopt || adopted) return;
+        adopted = true;
+        (void)hipFree(const_cast<int32_t *>(idx0[0]));
+        (void)hipFree(const_cast<int32_t *>(colind[0]));
+        if (values && values[0]) (void)hipFree(const_cast<void *>(values[0]));
+    };
+    if (int rc = need_init()) return drop_adopted(), rc;
     if (format != PYGIM_CSR && format != PYGIM_COO) return fail(PYGIM_ERR_INVALID, "format must be CSR(0) or COO(1)");
     const size_t es = dtype_size(dtype);
     if (es == 0) return fail(PYGIM_ERR_INVALID, "unknown dtype");
@@ -229,6 +242,7 @@ int pygim_group_create(int format, int dtype, int n_parts, const int32_t *const 
     int rc = 0;
     auto bail = [&](int code) {
         (void)hipDeviceSynchronize();
+        drop_adopted();
         free_group(g);
         return code;
     };
@@ -268,6 +282,11 @@ int pygim_group_create(int format, int dtype, int n_parts, const int32_t *const 
         }
         if (format == PYGIM_CSR) {
             if ((rc = to_device<uint32_t>(idx0[i], (size_t)(p.nrows + 1) * 4, &p.rowptr, &p.own_rowptr, st))) return bail(rc);
+            if (adopt) {
+                p.own_rowptr = p.own_colind = true;
+                if (p.vals) p.own_vals = true;
+                adopted = true;
+            }
             hipLaunchKernelGGL(k_check_csr, dim3((unsigned)((std::max(p.nrows + 1, p.nnz) + 255) / 256)), dim3(256), 0,
                                st, p.rowptr, p.colind, (uint32_t)p.nrows, (uint32_t)p.nnz, (uint32_t)p.ncols,
                                g->d_flags);
@@ -330,6 +349,129 @@ int pygim_group_create(int format, int dtype, int n_parts, const int32_t *const 
     }
     *out_handle = (int64_t) reinterpret_cast<uintptr_t>(g);
     return 0;
+}
+
+extern "C" {
+
+int pygim_group_create(int format, int dtype, int n_parts, const int32_t *const *idx0,
+                       const int32_t *const *colind, const void *const *values, const int64_t *nrows,
+                       const int64_t *ncols, const int64_t *nnz, const int64_t *n_dense,
+                       const int64_t *dense_cols, int64_t h_size, int64_t *out_handle) {
+    return group_create(format, dtype, n_parts, idx0, colind, values, nrows, ncols, nnz, n_dense, dense_cols, h_size,
+                        out_handle, /*adopt=*/false);
+}
+
+int pygim_group_create_transposed(int format, int dtype, int n_parts, const int32_t *const *idx0,
+                                  const int32_t *const *colind, const void *const *values, const int64_t *nrows,
+                                  const int64_t *ncols, const int64_t *nnz, const int64_t *n_dense,
+                                  const int64_t *dense_cols, int64_t h_size, int64_t *out_handle) {
+    // the argument checks of pygim_group_create, then its validation kernels on the input as given
+    if (int rc = need_init()) return rc;
+    if (format != PYGIM_CSR && format != PYGIM_COO) return fail(PYGIM_ERR_INVALID, "format must be CSR(0) or COO(1)");
+    const size_t es = dtype_size(dtype);
+    if (es == 0) return fail(PYGIM_ERR_INVALID, "unknown dtype");
+    if (n_parts <= 0 || !idx0 || !colind || !nrows || !ncols || !nnz || !n_dense || !dense_cols || !out_handle)
+        return fail(PYGIM_ERR_INVALID, "null argument or n_parts <= 0");
+    if (h_size <= 0) return fail(PYGIM_ERR_INVALID, "h_size must be positive");
+    uint64_t total_cols = 0, total_nnz = 0;
+    size_t dpos = 0;
+    for (int i = 0; i < n_parts; i++) {
+        if (nrows[i] != nrows[0]) return fail(PYGIM_ERR_INVALID, "all sparse parts must have the same number of rows");
+        if (nrows[i] < 0 || ncols[i] < 0 || nnz[i] < 0 || nnz[i] > 0xFFFFFFFFll || nrows[i] >= 0xFFFFFFFFll || ncols[i] > 0xFFFFFFFFll)
+            return fail(PYGIM_ERR_INVALID, "part sizes must fit 32-bit indices (the reference's uint32 matrices)");
+        if (n_dense[i] <= 0) return fail(PYGIM_ERR_INVALID, "n_dense must be positive");
+        int64_t sum = 0;
+        for (int64_t j = 0; j < n_dense[i]; j++) {
+            if (dense_cols[dpos + j] < 0) return fail(PYGIM_ERR_INVALID, "negative dense width");
+            sum += dense_cols[dpos + j];
+        }
+        dpos += (size_t)n_dense[i];
+        if (sum != h_size) return fail(PYGIM_ERR_INVALID, "dense widths of a part must add up to h_size");
+        if (!idx0[i] && (format == PYGIM_CSR || nnz[i] > 0)) return fail(PYGIM_ERR_INVALID, "null index array");
+        if (!colind[i] && nnz[i] > 0) return fail(PYGIM_ERR_INVALID, "null colind");
+        total_cols += (uint64_t)ncols[i];
+        total_nnz += (uint64_t)nnz[i];
+    }
+    if (total_cols >= 0xFFFFFFFFull || total_nnz > 0xFFFFFFFFull)
+        return fail(PYGIM_ERR_INVALID, "A^T must fit 32-bit indices: sum(ncols) rows, sum(nnz) entries");
+    hipStream_t st = nullptr;
+    // the input on the device: host arrays uploaded once, device arrays used in place
+    struct Held { void *p = nullptr; bool own = false; };
+    std::vector<Held> held;
+    int *d_flags = nullptr;
+    auto release_input = [&]() {
+        (void)hipDeviceSynchronize();
+        for (Held &x : held)
+            if (x.own && x.p) (void)hipFree(x.p);
+        held.clear();
+        if (d_flags) (void)hipFree(d_flags);
+        d_flags = nullptr;
+    };
+    auto bail = [&](int code) {
+        release_input();
+        return code;
+    };
+    if (hipMalloc((void **)&d_flags, 8 * sizeof(int)) != hipSuccess) return bail(fail(PYGIM_ERR_HIP, "hipMalloc flags"));
+    if (hipMemsetAsync(d_flags, 0, 8 * sizeof(int), st) != hipSuccess) return bail(fail(PYGIM_ERR_HIP, "memset flags"));
+    std::vector<TrPart> tp(n_parts);
+    int rc = 0;
+    for (int i = 0; i < n_parts; i++) {
+        const uint32_t nr = (uint32_t)nrows[i], nc = (uint32_t)ncols[i], nz = (uint32_t)nnz[i];
+        Held hc, hi, hv;
+        uint32_t *d_col = nullptr, *d_idx = nullptr;
+        void *d_val = nullptr;
+        rc = to_device<uint32_t>(colind[i], (size_t)nz * 4, &d_col, &hc.own, st);
+        hc.p = d_col;
+        held.push_back(hc);
+        if (rc) return bail(rc);
+        const size_t idx_bytes = format == PYGIM_CSR ? (size_t)(nr + 1ull) * 4 : (size_t)nz * 4;
+        rc = to_device<uint32_t>(idx0[i], idx_bytes, &d_idx, &hi.own, st);
+        hi.p = d_idx;
+        held.push_back(hi);
+        if (rc) return bail(rc);
+        const void *v = values ? values[i] : nullptr;
+        if (v) {
+            rc = to_device<void>(v, (size_t)nz * es, &d_val, &hv.own, st);
+            hv.p = d_val;
+            held.push_back(hv);
+            if (rc) return bail(rc);
+        }
+        if (format == PYGIM_CSR) {
+            hipLaunchKernelGGL(k_check_csr, dim3((unsigned)((std::max<uint64_t>(nr + 1ull, nz) + 255) / 256)), dim3(256), 0, st, d_idx, d_col, nr, nz,
+                               nc, d_flags);
+        } else if (nz > 0) {
+            hipLaunchKernelGGL(k_check_coo, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, d_idx, d_col, nz, nr, nc, d_flags);
+        }
+        tp[i] = TrPart{d_idx, d_col, d_val, nr, nc, nz, format == PYGIM_CSR ? 1 : 0};
+    }
+    int flags[4] = {0, 0, 0, 0};
+    if (hipMemcpy(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost) != hipSuccess)
+        return bail(fail(PYGIM_ERR_HIP, std::string("group validation: ") + hipGetErrorString(hipGetLastError())));
+    if (flags[1]) return bail(fail(PYGIM_ERR_INVALID, "index out of range in a sparse part"));
+    if (flags[0]) {
+        if (format == PYGIM_COO) return bail(fail(PYGIM_ERR_UNSORTED, "COO row indices are not sorted (pass a coalesced tensor)"));
+        return bail(fail(PYGIM_ERR_INVALID, "rowptr is not a non-decreasing prefix array ending at nnz"));
+    }
+    // the transpose (transpose_dev.hpp), then the creation path of any group: unit weights, plans, code streams and fallbacks as usual
+    uint32_t *rowptrT = nullptr, *colT = nullptr;
+    void *valsT = nullptr;
+    uint64_t nT = 0, nnzT = 0;
+    std::string err;
+    switch (dtype) {
+        case PYGIM_INT8: rc = tr_build_t<uint8_t>(tp, (uint8_t)1, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+        case PYGIM_INT16: rc = tr_build_t<uint16_t>(tp, (uint16_t)1, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+        case PYGIM_INT32: rc = tr_build_t<uint32_t>(tp, 1u, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+        case PYGIM_INT64: rc = tr_build_t<uint64_t>(tp, 1ull, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+        case PYGIM_FLT32: rc = tr_build_t<uint32_t>(tp, 0x3F800000u, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+        default: rc = tr_build_t<uint64_t>(tp, 0x3FF0000000000000ull, &rowptrT, &colT, &valsT, &nT, &nnzT, st, &err); break;
+    }
+    release_input();
+    if (rc) return fail(rc, err);
+    const int32_t *idx_t[1] = {(const int32_t *)rowptrT}, *col_t[1] = {(const int32_t *)colT};
+    const void *val_t[1] = {valsT};
+    const int64_t nrows_t[1] = {(int64_t)nT}, ncols_t[1] = {nrows[0]}, nnz_t[1] = {(int64_t)nnzT}, nd_t[1] = {1}, dc_t[1] = {h_size};
+    return group_create(PYGIM_CSR, dtype, 1, idx_t, col_t, valsT ? val_t : nullptr, nrows_t, ncols_t, nnz_t, nd_t, dc_t, h_size, out_handle,
+                        /*adopt=*/true);
 }
 
 int pygim_group_free(int64_t handle) {
@@ -444,6 +586,28 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
         case PYGIM_INT32: return launch_dequantize<int32_t>((const int32_t *)Q, (uint64_t)n, absmax_bits, k, out, st);
         default: return launch_dequantize<float>((const float *)Q, (uint64_t)n, absmax_bits, k, out, st);
     }
+}
+
+int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *G, int64_t ldg,
+                const void *X, int64_t ldx, int64_t h, void *out, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "sddmm: type must be FLT32 or DBL64");
+    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0xFFFFFFFFll - SD_EPW || h < 1 || h > 0xFFFFFFFFll || ldg < h || ldx < h)
+        return fail(PYGIM_ERR_INVALID, "bad sddmm sizes / strides");
+    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "sddmm: entries without rows");
+    if (!rowptr || (nnz > 0 && (!colind || !G || !X || !out))) return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / G / X / out");
+    if (!is_device_ptr(rowptr) || (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(G) || !is_device_ptr(X) || !is_device_ptr(out))))
+        return fail(PYGIM_ERR_INVALID, "pygim_sddmm needs device pointers");
+    if (nnz == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PYGIM_FLT32)
+        launch_sddmm<float>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const float *)G, (uint64_t)ldg,
+                            (const float *)X, (uint64_t)ldx, (uint32_t)h, (float *)out, st);
+    else
+        launch_sddmm<double>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const double *)G, (uint64_t)ldg,
+                             (const double *)X, (uint64_t)ldx, (uint32_t)h, (double *)out, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int pygim_group_timers(int64_t handle, double out_ms[5]) {

@@ -1,0 +1,157 @@
+// sddmm_dev.hpp -- sampled dense-dense product on a caller's CSR: out[e] = sum_f G[row(e), f] * X[colind[e], f] for every stored entry e
+// (the gradient of a conv layer's aggregation with respect to the edge values: d(A . X)/dA[r, c] = G[r] . X[c]).
+//
+// Shape (the gather of the forward's sweep, with one dot product per entry instead of a sum per row):
+//   * a wave owns SD_EPW consecutive entries (a hub row is cut across waves; no output is shared, so there are no atomics and every
+//     run stores the same bits) and walks them in batches of 64;
+//   * a lane group of L lanes (L = the power of two that covers h in 16-byte pieces, at most 64) holds one X row per wave-instruction,
+//     16 bytes per lane; 64 / L groups work on different entries side by side, every lane keeps the partial sums of the L entries its
+//     group handles in a batch and issues their gathers back to back (several rows in flight);
+//   * a batch inside one row keeps G[row] in registers; a batch that crosses rows reads each entry's G row beside its X row;
+//   * the L partials of a group are reduced as a reduce-scatter (recursive halving: L - 1 exchanges per lane for L entries, instead of
+//     a log2(L)-step tree per entry) that leaves the sum of the group's k-th entry in its k-th lane -- the 64 sums of a batch then sit in
+//     64 lanes, and one coalesced store writes them.
+// The order of every sum is fixed (per lane: features in ascending order within its pieces; then the halving order): deterministic.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pygim {
+
+constexpr uint32_t SD_EPW = 256;   // entries per wave (4 batches of 64)
+
+// the last row r < nrows with rowptr[r] <= e, searched in [lo, nrows)
+__device__ inline uint32_t sd_row_of(const uint32_t *__restrict__ rowptr, uint32_t lo, uint32_t nrows, uint32_t e) {
+    uint32_t hi = nrows;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (rowptr[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <typename T, int VEC> struct SdVec { typedef T __attribute__((ext_vector_type(VEC))) type; };
+template <typename T> struct SdVec<T, 1> { typedef T type; };
+
+template <typename T, int VEC>
+__device__ inline T sd_dot(const typename SdVec<T, VEC>::type &a, const typename SdVec<T, VEC>::type &b) {
+    if constexpr (VEC == 1) {
+        return a * b;
+    } else {
+        T s = a[0] * b[0];
+#pragma unroll
+        for (int i = 1; i < VEC; i++) s += a[i] * b[i];
+        return s;
+    }
+}
+
+// a wave-uniform value of lane `src` (src a compile-time constant after unrolling when the whole wave is one group)
+template <int L> __device__ inline uint32_t sd_take(uint32_t v, uint32_t src) {
+    if constexpr (L == 64) return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
+    else return (uint32_t)__shfl((int)v, (int)src, 64);
+}
+
+// NVC: 16-byte pieces per lane held at once (features per lane and pass = NVC * VEC; wider rows take several passes)
+template <typename T, int VEC, int L, int NVC>
+__global__ __launch_bounds__(256) void k_sddmm(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
+                                               const T *__restrict__ G, uint64_t ldg, const T *__restrict__ X, uint64_t ldx, uint32_t h, T *__restrict__ out) {
+    using V = typename SdVec<T, VEC>::type;
+    constexpr int R = 64 / L;   // entries side by side per wave-instruction
+    const uint32_t lane = threadIdx.x & 63, grp = lane / L, li = lane % L;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint64_t e_begin = wave * SD_EPW;
+    if (e_begin >= nnz) return;
+    const uint32_t e_end = (uint32_t)(e_begin + SD_EPW < nnz ? e_begin + SD_EPW : nnz);
+    const uint32_t nv = (h + VEC * L - 1) / (VEC * L);   // pieces per lane and entry
+    uint32_t row = sd_row_of(rowptr, 0, nrows, (uint32_t)e_begin);
+    for (uint32_t base = (uint32_t)e_begin; base < e_end; base += 64) {
+        const uint32_t bend = base + 64 < e_end ? base + 64 : e_end;
+        if (rowptr[row + 1] <= base) row = sd_row_of(rowptr, row + 1, nrows, base);
+        const bool one_row = rowptr[row + 1] >= bend;   // wave-uniform
+        // entry base + lane: its column (and, when the batch crosses rows, its row); the groups take theirs from these lanes
+        const uint32_t my_e = base + lane;
+        const uint32_t my_col = my_e < bend ? colind[my_e] : 0u;
+        uint32_t my_row = row;
+        if (!one_row && my_e < bend) my_row = sd_row_of(rowptr, row, nrows, my_e);
+        T p[L];
+#pragma unroll
+        for (int k = 0; k < L; k++) p[k] = T(0);
+        for (uint32_t c0 = 0; c0 < nv; c0 += NVC) {
+            V gv[NVC];
+            if (one_row) {
+                const T *gr = G + (uint64_t)row * ldg;
+#pragma unroll
+                for (int v = 0; v < NVC; v++) {
+                    const uint32_t f = ((c0 + v) * L + li) * VEC;
+                    gv[v] = (c0 + v < nv && f < h) ? *(const V *)(gr + f) : V(0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < L; k++) {
+                const uint32_t src = grp + (uint32_t)(R * k);
+                const bool valid = base + src < bend;
+                const uint32_t col = sd_take<L>(my_col, src);
+                const T *xr = X + (uint64_t)col * ldx;
+                const T *gr = G + (uint64_t)(one_row ? row : sd_take<L>(my_row, src)) * ldg;
+#pragma unroll
+                for (int v = 0; v < NVC; v++) {
+                    const uint32_t f = ((c0 + v) * L + li) * VEC;
+                    if (valid && c0 + v < nv && f < h) {
+                        const V xv = *(const V *)(xr + f);
+                        const V gg = one_row ? gv[v] : *(const V *)(gr + f);
+                        p[k] += sd_dot<T, VEC>(gg, xv);
+                    }
+                }
+            }
+        }
+        // reduce-scatter over the group's L lanes: after the step of distance s a lane keeps the half of its partials whose index has
+        // bit s equal to its own lane bit s, and adds the partner's copy of that half -- in the end lane li holds entry li's sum
+#pragma unroll
+        for (int s = L / 2; s >= 1; s >>= 1) {
+            const bool hi = (li & (uint32_t)s) != 0;
+#pragma unroll
+            for (int j = 0; j < s; j++) {
+                const T send = hi ? p[j] : p[j + s];
+                const T keep = hi ? p[j + s] : p[j];
+                p[j] = keep + __shfl_xor(send, s, 64);
+            }
+        }
+        const uint32_t e = base + grp + (uint32_t)R * li;   // a permutation of the batch's 64 entries over the 64 lanes
+        if (e < bend) out[e] = p[0];
+    }
+}
+
+template <typename T, int VEC, int L>
+inline void launch_sddmm_l(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+                           uint32_t h, T *out, hipStream_t st) {
+    const uint64_t waves = ((uint64_t)nnz + SD_EPW - 1) / SD_EPW;
+    // pieces held at once: the whole row up to 4 pieces (h = 256 FLT32 / DBL64 with 64 lanes: 1 / 2), longer rows in passes of 4
+    hipLaunchKernelGGL((k_sddmm<T, VEC, L, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out);
+}
+
+template <typename T, int VEC>
+inline void launch_sddmm_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+                           uint32_t h, T *out, hipStream_t st) {
+    const uint32_t pieces = (h + VEC - 1) / VEC;
+    if (pieces <= 1) launch_sddmm_l<T, VEC, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 2) launch_sddmm_l<T, VEC, 2>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 4) launch_sddmm_l<T, VEC, 4>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 8) launch_sddmm_l<T, VEC, 8>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 16) launch_sddmm_l<T, VEC, 16>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 32) launch_sddmm_l<T, VEC, 32>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else launch_sddmm_l<T, VEC, 64>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+}
+
+// 16-byte pieces when every row of G and X starts 16-byte aligned and h fills whole pieces; else one element per lane
+template <typename T>
+inline void launch_sddmm(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+                         uint32_t h, T *out, hipStream_t st) {
+    constexpr uint32_t V = 16 / sizeof(T);
+    const bool vec = h % V == 0 && ldg % V == 0 && ldx % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)X % 16 == 0;
+    if (vec) launch_sddmm_v<T, (int)V>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else launch_sddmm_v<T, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+}
+
+}  // namespace pygim
