@@ -210,6 +210,32 @@ int pygim_spmm_run_dequant(int64_t handle, const void *Xq, int64_t ldx, float *o
 int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *G,
                 int64_t ldg, const void *X, int64_t ldx, int64_t h, void *out, void *stream);
 
+/* ---- products and softmax whose edge values are an operand of the call (attention, gates, learned normalisation) ----
+ * Functional entry points on a caller's CSR like pygim_sddmm: no group handle, device pointers only, FLT32 and DBL64 only (else
+ * PYGIM_ERR_INVALID), int32 rowptr / colind with nnz <= 2^31 - 1, a valid CSR guaranteed by the caller.  nnz = 0, empty rows and any
+ * h >= 1 are allowed.  They only enqueue work on `stream`: no allocation, no synchronisation.  Scratch comes from the caller:
+ * `workspace` holds at least the bytes the matching *_workspace function returns (a function of its arguments alone, never of the
+ * CSR's contents; -1 for bad arguments), is 16-byte aligned, and must not be shared by calls that may overlap.  No float atomics:
+ * rows cut across waves leave partial results in the workspace and a second kernel folds them in a fixed order, so every launch
+ * stores the same bits.
+ *
+ *   pygim_spmm_values:  out[r, f] = sum over the entries e of row r of values[e * heads + f / (h / heads)] * X[colind[e], f]
+ *     values: [nnz, heads] contiguous, heads >= 1 divides h; X: row stride ldx >= h; out[0:nrows, 0:h] (row stride ldo >= h) is
+ *     overwritten, empty rows with zeros.  Within 1e-5 (FLT32) / 1e-12 (DBL64) of sum |value . x| of the exact value.
+ *   pygim_edge_softmax:  out[e, k] = exp(s[e, k] - m) / sum_{e' in row(e)} exp(s[e', k] - m), m the row's and head's maximum;
+ *     scores and out: [nnz, heads] contiguous; the sum runs over the row's stored entries (duplicates are separate entries); stable
+ *     for finite scores of any magnitude.
+ *   pygim_edge_softmax_backward:  out[e, k] = P[e, k] * (dP[e, k] - sum_{e' in row(e)} P[e', k] * dP[e', k]).                */
+int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
+int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values,
+                      int64_t heads, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int64_t pygim_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t heads);
+int pygim_edge_softmax(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *scores, int64_t heads, void *out,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *P, const void *dP,
+                                int64_t heads, void *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- introspection -----------------------------------------------------------
  * Milliseconds of the last host-pointer run, in the reference's Timer buckets
  * (support/timer.h; printed as [DATA] lines, spmm_mul_csr.c:563-580):

@@ -9,7 +9,9 @@ Layout:
   synth.py         seeded synthetic graphs in the shapes BASELINE.json names
   dist.py          sp_parts / ds_parts across the GPUs of one node (torch.distributed/RCCL)
   autograd.py      gradients of ``mul``: A^T . G through a transposed group, the edge values' SDDMM (``sddmm``)
+  attention.py     products and softmax with per-call edge values (``EdgeGraph``, ``spmm_values``, ``edge_softmax``)
 """
 __version__ = "0.1.0"
 
+from .attention import EdgeGraph, edge_softmax, spmm_values  # noqa: E402,F401
 from .autograd import sddmm  # noqa: E402,F401

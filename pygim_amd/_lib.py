@@ -21,6 +21,7 @@ EXPORTS = [
     "pygim_quant_spmm_run_post", "pygim_generation", "pygim_group_lds_plan", "pygim_group_lds_code", "pygim_group_lds_geometry", "pygim_group_lds_note",
     "pygim_group_lds_tiles", "pygim_group_lds_runs", "pygim_group_serial", "pygim_group_host_windows",
     "pygim_group_create_transposed", "pygim_sddmm",
+    "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -61,6 +62,13 @@ def lib():
                                          p_i64]
         L.pygim_group_create_transposed.argtypes = list(L.pygim_group_create.argtypes)
         L.pygim_sddmm.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, vp, vp]
+        L.pygim_spmm_values.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp]
+        L.pygim_spmm_values_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
+        L.pygim_spmm_values_workspace.restype = c_i64
+        L.pygim_edge_softmax.argtypes = [c_int, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_edge_softmax_backward.argtypes = [c_int, c_i64, vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_edge_softmax_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
+        L.pygim_edge_softmax_workspace.restype = c_i64
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -172,6 +180,44 @@ def sddmm(dtype, nrows, rowptr_ptr, col_ptr, nnz, g_ptr, ldg, x_ptr, ldx, h, out
     check(lib().pygim_sddmm(int(dtype), int(nrows), ctypes.c_void_p(rowptr_ptr or None), ctypes.c_void_p(col_ptr or None), int(nnz),
                             ctypes.c_void_p(g_ptr or None), int(ldg), ctypes.c_void_p(x_ptr or None), int(ldx), int(h),
                             ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
+
+
+def _vp(p):
+    return ctypes.c_void_p(p or None)
+
+
+def spmm_values_workspace(dtype, nrows, nnz, h, heads):
+    """bytes of scratch spmm_values needs for this shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_values_workspace(int(dtype), int(nrows), int(nnz), int(h), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_values_workspace arguments")
+    return n
+
+
+def spmm_values(dtype, nrows, rowptr_ptr, col_ptr, nnz, val_ptr, heads, x_ptr, ldx, h, out_ptr, ldo, ws_ptr, ws_bytes, stream=0):
+    """out[r, f] = sum_e values[e, head of f] * X[col[e], f] over the entries of row r (device pointers; FLT32 / DBL64)"""
+    check(lib().pygim_spmm_values(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(val_ptr), int(heads), _vp(x_ptr),
+                                  int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def edge_softmax_workspace(dtype, nrows, nnz, heads):
+    """bytes of scratch edge_softmax / edge_softmax_backward need for this shape"""
+    n = int(lib().pygim_edge_softmax_workspace(int(dtype), int(nrows), int(nnz), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad edge_softmax_workspace arguments")
+    return n
+
+
+def edge_softmax(dtype, nrows, rowptr_ptr, nnz, scores_ptr, heads, out_ptr, ws_ptr, ws_bytes, stream=0):
+    """softmax of scores [nnz, heads] over the stored entries of every row, per head"""
+    check(lib().pygim_edge_softmax(int(dtype), int(nrows), _vp(rowptr_ptr), int(nnz), _vp(scores_ptr), int(heads), _vp(out_ptr),
+                                   _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def edge_softmax_backward(dtype, nrows, rowptr_ptr, nnz, p_ptr, dp_ptr, heads, out_ptr, ws_ptr, ws_bytes, stream=0):
+    """out = P * (dP - sum_row P * dP): the gradient of edge_softmax with respect to the scores"""
+    check(lib().pygim_edge_softmax_backward(int(dtype), int(nrows), _vp(rowptr_ptr), int(nnz), _vp(p_ptr), _vp(dp_ptr), int(heads),
+                                            _vp(out_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
 
 
 def group_free(handle):

@@ -1,0 +1,222 @@
+"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax`` and the structure they share.
+
+A device group (``to_pim_group``) freezes its edge values when it is created -- on the fast path they are compiled into the code
+stream -- so ``mul`` multiplies by those values for as long as the group lives.  Values that change between calls (attention
+weights, gates, a normalisation derived from learned quantities, or simply edge weights after ``optimizer.step()``) go through the
+functions here instead: hand-written gfx950 kernels on the plain CSR (pygim_spmm_values, pygim_edge_softmax,
+pygim_edge_softmax_backward: no atomics, the same bits on every run), differentiable in every floating operand.
+
+* :class:`EdgeGraph` holds the structure once, on the device: int32 ``rowptr`` / ``col``, the row of every entry, and -- built on the
+  first backward -- the transposed structure with the permutation that carries per-entry values over to it.
+* :func:`spmm_values` ``out[r] = sum_e value[e, head] * X[col[e]]``; backward ``dX`` = the same kernel on the transposed structure,
+  ``dvalue`` = one ``pygim_sddmm`` per head on strided views of ``G`` and ``X``.
+* :func:`edge_softmax` the softmax of per-entry scores over the stored entries of every row, per head.
+
+Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph.
+"""
+from __future__ import annotations
+
+import torch
+
+FLOAT_TYPES = (torch.float32, torch.float64)
+
+
+def _backend():
+    from . import pim_ops
+
+    L = pim_ops._lib
+    if not L.is_initialized():
+        L.init_ranks(1)
+    return L, pim_ops.DTYPE_CODE
+
+
+def _device_for(t: torch.Tensor) -> torch.device:
+    if t.is_cuda or not torch.cuda.is_available():
+        return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+class EdgeGraph:
+    """the CSR structure of an adjacency, on the device, for :func:`spmm_values` and :func:`edge_softmax`
+
+    ``rowptr`` [nrows + 1] and ``col`` [nnz] (any integer type, entries in stored order; duplicates and empty rows allowed);
+    ``sparse_sizes`` = (rows, columns).  The CSR is checked here, once: the kernels trust it."""
+
+    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, sparse_sizes):
+        nrows, ncols = int(sparse_sizes[0]), int(sparse_sizes[1])
+        if rowptr.dim() != 1 or col.dim() != 1 or rowptr.numel() != nrows + 1 or nrows < 0 or ncols < 0:
+            raise ValueError(f"EdgeGraph: rowptr must have {nrows + 1} elements (sparse_sizes {tuple(sparse_sizes)}), got {tuple(rowptr.shape)}")
+        nnz = col.numel()
+        if nnz > 2 ** 31 - 1:
+            raise ValueError("EdgeGraph: more than 2^31 - 1 entries")
+        dev = _device_for(col)
+        rp = rowptr.to(dev, torch.int64)
+        cc = col.to(dev, torch.int64)
+        bad = (rp[0] != 0) | (rp[-1] != nnz) | (rp[1:] < rp[:-1]).any()
+        if nnz > 0:
+            bad = bad | (cc.min() < 0) | (cc.max() >= ncols)
+        if bool(bad):
+            raise ValueError("EdgeGraph: rowptr must rise from 0 to nnz and every column must lie inside sparse_sizes")
+        self.nrows, self.ncols, self.nnz, self.device = nrows, ncols, nnz, dev
+        self.rowptr = rp.to(torch.int32).contiguous()
+        self.col = cc.to(torch.int32).contiguous()
+        self.row = torch.repeat_interleave(torch.arange(nrows, device=dev, dtype=torch.int32), rp[1:] - rp[:-1])
+        self._t = None
+
+    @classmethod
+    def _bare(cls, rowptr, col, row, nrows, ncols):
+        g = cls.__new__(cls)
+        g.nrows, g.ncols, g.nnz, g.device = nrows, ncols, col.numel(), col.device
+        g.rowptr, g.col, g.row, g._t = rowptr, col, row, None
+        return g
+
+    @classmethod
+    def of(cls, adj) -> "EdgeGraph":
+        """the graph of a SparseTensor / SparseTensorShim, of a ``backend_pim`` wrapper (its ``.raw``) or of an EdgeGraph; cached on
+        the object it was made from"""
+        if isinstance(adj, cls):
+            return adj
+        held = getattr(adj, "_edge_graph", None)
+        if isinstance(held, cls):
+            return held
+        raw = adj.raw if hasattr(adj, "raw") and hasattr(adj.raw, "csr") else adj
+        if not hasattr(raw, "csr"):
+            raise TypeError(f"EdgeGraph.of: expected a SparseTensor, a backend_pim wrapper or an EdgeGraph, got {type(adj).__name__}")
+        rowptr, col, _ = raw.csr()
+        g = cls(rowptr, col, (raw.size(0), raw.size(1)))
+        try:
+            adj._edge_graph = g
+        except AttributeError:
+            pass
+        return g
+
+    def transposed(self):
+        """(graph of A^T, perm): entry i of A^T is entry perm[i] of A -- the stable sort of the entries by column, the order
+        pygim_group_create_transposed defines"""
+        if self._t is None:
+            perm = torch.argsort(self.col.long(), stable=True)
+            counts = torch.bincount(self.col.long(), minlength=self.ncols)
+            rowptr_t = torch.zeros(self.ncols + 1, dtype=torch.int64, device=self.device)
+            torch.cumsum(counts, 0, out=rowptr_t[1:])
+            col_t = self.row[perm].contiguous()
+            row_t = self.col[perm].contiguous()
+            self._t = (EdgeGraph._bare(rowptr_t.to(torch.int32), col_t, row_t, self.ncols, self.nrows), perm)
+        return self._t
+
+
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+
+
+def _run_spmm_values(g: EdgeGraph, value: torch.Tensor, X: torch.Tensor, heads: int) -> torch.Tensor:
+    """value [nnz, heads] and X [ncols, h] contiguous on g.device -> [nrows, h]"""
+    L, code = _backend()
+    h = X.size(1)
+    out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
+    if g.nrows == 0:
+        return out
+    nbytes = L.spmm_values_workspace(code[X.dtype], g.nrows, g.nnz, h, heads)
+    ws = _workspace(nbytes, g.device)
+    L.spmm_values(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, value.data_ptr(), heads, X.data_ptr(), X.stride(0), h,
+                  out.data_ptr(), h, ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out
+
+
+class SpmmValues(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, value, X, heads):
+        ctx.g, ctx.heads = g, heads
+        ctx.save_for_backward(value, X)
+        return _run_spmm_values(g, value, X, heads)
+
+    @staticmethod
+    def backward(ctx, G):
+        g, heads = ctx.g, ctx.heads
+        value, X = ctx.saved_tensors
+        G = G.contiguous()
+        dvalue = dX = None
+        if ctx.needs_input_grad[2]:
+            gt, perm = g.transposed()
+            dX = _run_spmm_values(gt, value.index_select(0, perm), G, heads)
+        if ctx.needs_input_grad[1]:
+            L, code = _backend()
+            h = X.size(1)
+            hd, es = h // heads, X.element_size()
+            per_head = torch.empty((heads, g.nnz), dtype=X.dtype, device=g.device)
+            if g.nnz > 0:
+                for k in range(heads):   # G[:, k * hd:(k + 1) * hd] . X[:, k * hd:(k + 1) * hd] per entry: strided views of both
+                    L.sddmm(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
+                            X.data_ptr() + k * hd * es, X.stride(0), hd, per_head[k].data_ptr(), _stream(g.device))
+            dvalue = per_head.t().contiguous()
+        return None, dvalue, dX, None
+
+
+def spmm_values(graph, value: torch.Tensor, X: torch.Tensor, heads: int = 1) -> torch.Tensor:
+    """``out[r, f] = sum over the stored entries e of row r of value[e, f // (h // heads)] * X[col[e], f]``
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; value [nnz] (heads = 1) or [nnz, heads]; X [columns, h] with
+    ``h % heads == 0``; value and X both float32 or both float64.  Differentiable in value and X.  Runs on the device; CPU tensors are
+    staged there and the result comes back to X's device."""
+    g = EdgeGraph.of(graph)
+    heads = int(heads)
+    if X.dtype not in FLOAT_TYPES or value.dtype != X.dtype:
+        raise TypeError(f"spmm_values: value and X must both be float32 or float64, got {value.dtype} and {X.dtype}")
+    if X.dim() != 2 or X.size(0) != g.ncols:
+        raise ValueError(f"spmm_values: X must be [{g.ncols}, h], got {tuple(X.shape)}")
+    if heads < 1 or X.size(1) < 1 or X.size(1) % heads != 0:
+        raise ValueError(f"spmm_values: heads = {heads} must divide h = {X.size(1)}")
+    if value.dim() == 1 and heads == 1:
+        value = value.unsqueeze(1)
+    if value.dim() != 2 or value.size(0) != g.nnz or value.size(1) != heads:
+        raise ValueError(f"spmm_values: value must be [{g.nnz}] or [{g.nnz}, {heads}], got {tuple(value.shape)}")
+    home = X.device
+    out = SpmmValues.apply(g, value.to(g.device).contiguous(), X.to(g.device).contiguous(), heads)
+    return out.to(home)
+
+
+def _run_edge_softmax(g: EdgeGraph, a: torch.Tensor, b, heads: int) -> torch.Tensor:
+    L, code = _backend()
+    out = torch.empty_like(a)
+    if g.nnz == 0:
+        return out
+    ws = _workspace(L.edge_softmax_workspace(code[a.dtype], g.nrows, g.nnz, heads), g.device)
+    if b is None:
+        L.edge_softmax(code[a.dtype], g.nrows, g.rowptr.data_ptr(), g.nnz, a.data_ptr(), heads, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                       _stream(g.device))
+    else:
+        L.edge_softmax_backward(code[a.dtype], g.nrows, g.rowptr.data_ptr(), g.nnz, a.data_ptr(), b.data_ptr(), heads, out.data_ptr(),
+                                ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out
+
+
+class EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, scores, heads):
+        ctx.g, ctx.heads = g, heads
+        P = _run_edge_softmax(g, scores, None, heads)
+        ctx.save_for_backward(P)
+        return P
+
+    @staticmethod
+    def backward(ctx, dP):
+        (P,) = ctx.saved_tensors
+        return None, _run_edge_softmax(ctx.g, P, dP.contiguous(), ctx.heads), None
+
+
+def edge_softmax(graph, scores: torch.Tensor) -> torch.Tensor:
+    """softmax of ``scores`` ([nnz] or [nnz, heads], float32 / float64, one score per stored entry and head) over the stored entries
+    of every row, per head: ``exp(s - max) / sum exp(s - max)``; duplicates are separate entries.  Differentiable; same shape as
+    ``scores``, on its device."""
+    g = EdgeGraph.of(graph)
+    if scores.dtype not in FLOAT_TYPES:
+        raise TypeError(f"edge_softmax: scores must be float32 or float64, got {scores.dtype}")
+    if scores.dim() not in (1, 2) or scores.size(0) != g.nnz or (scores.dim() == 2 and scores.size(1) < 1):
+        raise ValueError(f"edge_softmax: scores must be [{g.nnz}] or [{g.nnz}, heads], got {tuple(scores.shape)}")
+    heads = 1 if scores.dim() == 1 else scores.size(1)
+    home = scores.device
+    P = EdgeSoftmax.apply(g, scores.to(g.device).reshape(g.nnz, heads).contiguous(), heads)
+    return P.reshape(scores.shape).to(home)

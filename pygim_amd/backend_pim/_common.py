@@ -186,6 +186,15 @@ class SparseGroupBase:
         pim_ops._lib.spmm_run_group(handle, [G.data_ptr()], out.data_ptr(), pim_ops._stream_of(out))
         return out[:self.raw.size(1)] if total_cols != self.raw.size(1) else out
 
+    # -- the product with values given per call (pygim_amd/attention.py) -----------------------------------
+    def mul_values(self, value: torch.Tensor, B: torch.Tensor, heads: int = 1):
+        """``out[r] = sum_e value[e, head] * B[col[e]]`` on the raw tensor's structure, in its CSR entry order: value [nnz] or
+        [nnz, heads], float32 / float64 like B.  ``mul`` multiplies by the values the group was created with; this is the product for
+        values that change between calls (no group is created or used).  Differentiable in value and B."""
+        from ..attention import EdgeGraph, spmm_values
+
+        return spmm_values(EdgeGraph.of(self), value, B, heads)
+
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):
         assert nparts > 0

@@ -23,6 +23,8 @@
 #endif
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
+#include "spmm_values_dev.hpp"
+#include "edge_softmax_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -608,6 +610,85 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
                              (const double *)X, (uint64_t)ldx, (uint32_t)h, (double *)out, st);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---- products and softmax with per-call edge values (spmm_values_dev.hpp, edge_softmax_dev.hpp) ----
+int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
+    (void)nrows;
+    (void)heads;
+    if ((dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) || nnz < 0 || h < 1) return -1;
+    return (int64_t)spmm_values_workspace_bytes((uint64_t)nnz, (uint64_t)h, dtype == PYGIM_FLT32 ? 4 : 8);
+}
+
+int64_t pygim_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t heads) {
+    (void)nrows;
+    if ((dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) || nnz < 0 || heads < 1) return -1;
+    return (int64_t)edge_softmax_workspace_bytes((uint64_t)nnz, (uint64_t)heads, dtype == PYGIM_FLT32 ? 4 : 8);
+}
+
+int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, int64_t heads,
+                      const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32 or DBL64");
+    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldx < h || ldo < h)
+        return fail(PYGIM_ERR_INVALID, "bad spmm_values sizes / strides");
+    if (heads < 1 || h % heads != 0) return fail(PYGIM_ERR_INVALID, "spmm_values: heads must divide h");
+    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "spmm_values: entries without rows");
+    if (!rowptr || (nrows > 0 && !out) || (nnz > 0 && (!colind || !values || !X)))
+        return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / values / X / out");
+    if (!is_device_ptr(rowptr) || (nrows > 0 && !is_device_ptr(out)) ||
+        (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(values) || !is_device_ptr(X))))
+        return fail(PYGIM_ERR_INVALID, "pygim_spmm_values needs device pointers");
+    const int64_t need = pygim_spmm_values_workspace(dtype, nrows, nnz, h, heads);
+    if (need > 0 && (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace)))
+        return fail(PYGIM_ERR_INVALID, "spmm_values: workspace too small, misaligned or not device memory (pygim_spmm_values_workspace)");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PYGIM_FLT32)
+        launch_spmm_values<float>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const float *)values, (uint32_t)heads,
+                                  (const float *)X, (uint64_t)ldx, (uint32_t)h, (float *)out, (uint64_t)ldo, (float *)workspace, st);
+    else
+        launch_spmm_values<double>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const double *)values,
+                                   (uint32_t)heads, (const double *)X, (uint64_t)ldx, (uint32_t)h, (double *)out, (uint64_t)ldo, (double *)workspace, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int edge_softmax_call(int mode, int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *a, const void *b, int64_t heads, void *out,
+                             void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "edge_softmax: type must be FLT32 or DBL64");
+    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || heads < 1 || heads > 0x7FFFFFFFll)
+        return fail(PYGIM_ERR_INVALID, "bad edge_softmax sizes");
+    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "edge_softmax: entries without rows");
+    const bool bwd = mode == ES_BACKWARD;
+    if (!rowptr || (nnz > 0 && (!a || !out || (bwd && !b)))) return fail(PYGIM_ERR_INVALID, "bad rowptr / scores / out");
+    if (!is_device_ptr(rowptr) || (nnz > 0 && (!is_device_ptr(a) || !is_device_ptr(out) || (bwd && !is_device_ptr(b)))))
+        return fail(PYGIM_ERR_INVALID, "pygim_edge_softmax needs device pointers");
+    if (nnz == 0) return 0;
+    const int64_t need = pygim_edge_softmax_workspace(dtype, nrows, nnz, heads);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace))
+        return fail(PYGIM_ERR_INVALID, "edge_softmax: workspace too small, misaligned or not device memory (pygim_edge_softmax_workspace)");
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *rp = (const uint32_t *)rowptr;
+    if (dtype == PYGIM_FLT32) {
+        if (bwd) launch_edge_softmax<float, ES_BACKWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const float *)a, (const float *)b, (uint32_t)heads, (float *)out, workspace, st);
+        else launch_edge_softmax<float, ES_FORWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const float *)a, nullptr, (uint32_t)heads, (float *)out, workspace, st);
+    } else {
+        if (bwd) launch_edge_softmax<double, ES_BACKWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const double *)a, (const double *)b, (uint32_t)heads, (double *)out, workspace, st);
+        else launch_edge_softmax<double, ES_FORWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const double *)a, nullptr, (uint32_t)heads, (double *)out, workspace, st);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pygim_edge_softmax(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *scores, int64_t heads, void *out, void *workspace,
+                       int64_t workspace_bytes, void *stream) {
+    return edge_softmax_call(ES_FORWARD, dtype, nrows, rowptr, nnz, scores, nullptr, heads, out, workspace, workspace_bytes, stream);
+}
+
+int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *P, const void *dP, int64_t heads, void *out,
+                                void *workspace, int64_t workspace_bytes, void *stream) {
+    return edge_softmax_call(ES_BACKWARD, dtype, nrows, rowptr, nnz, P, dP, heads, out, workspace, workspace_bytes, stream);
 }
 
 int pygim_group_timers(int64_t handle, double out_ms[5]) {

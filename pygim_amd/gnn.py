@@ -11,6 +11,9 @@ pyg_sage_conv.py:122-155), written on plain torch.nn (torch_geometric is not ins
 with aggregate = quantise -> adj_t.mul -> dequantise (pygim_amd/quantize.py).  ``adj_t`` is a
 SparseTensor (cpu path), a backend_pim SparseTensorCOO, or a pygim_amd.dist.RowShardAdj (multi-GPU:
 x and the result are then this rank's row block).
+
+GATConv / GAT are the attention layer on top of pygim_amd.attention: its edge weights are computed on every call, so its aggregation
+is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values frozen in the group); float32 / float64, trainable.
 """
 import torch
 import torch.nn.functional as F
@@ -48,6 +51,39 @@ class GINConv(torch.nn.Module):
 
     def forward(self, x, adj_t):
         return self.nn(message_and_aggregate(adj_t, x) + (1 + self.eps) * x)
+
+
+class GATConv(torch.nn.Module):
+    """PyG's GATConv arithmetic on the adjacency as given (no self loops are inserted, like the other layers here):
+    x' = lin(x) as [N, H, F];  score of stored entry (i, j) = leaky_relu(a_dst[i] + a_src[j]) with a = (x' * att).sum(-1);
+    p = softmax of the scores over the entries of row i;  out[i] = sum_j p[(i, j)] * x'[j] per head; heads concatenated or averaged."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, **_):
+        super().__init__()
+        self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
+        self.lin = Linear(in_channels, self.heads * self.out_channels, bias=False)
+        self.att_src = torch.nn.Parameter(torch.empty(1, self.heads, self.out_channels))
+        self.att_dst = torch.nn.Parameter(torch.empty(1, self.heads, self.out_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(self.heads * self.out_channels if self.concat else self.out_channels)) if bias else None
+        torch.nn.init.xavier_uniform_(self.lin.weight)
+        torch.nn.init.xavier_uniform_(self.att_src)
+        torch.nn.init.xavier_uniform_(self.att_dst)
+
+    def forward(self, x, adj_t):
+        from .attention import EdgeGraph, edge_softmax, spmm_values
+
+        g = EdgeGraph.of(adj_t)
+        H, F_ = self.heads, self.out_channels
+        xp = self.lin(x).view(-1, H, F_)
+        a_src = (xp * self.att_src).sum(-1)
+        a_dst = (xp * self.att_dst).sum(-1)
+        row, col = g.row.long().to(x.device), g.col.long().to(x.device)
+        score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
+        p = edge_softmax(g, score)
+        out = spmm_values(g, p, xp.reshape(-1, H * F_), heads=H)
+        if not self.concat:
+            out = out.view(-1, H, F_).mean(1)
+        return out if self.bias is None else out + self.bias
 
 
 def folded_epilogue(conv_bias, bn):
@@ -98,3 +134,10 @@ class GIN(_Stack):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5):
         mlp = lambda h: Sequential(Linear(h, h), BatchNorm1d(h), ReLU(), Linear(h, h))
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout, lambda h: GINConv(mlp(h)))
+
+
+class GAT(_Stack):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1):
+        assert hidden_channels % heads == 0, "GAT: heads must divide hidden_channels (the heads are concatenated)"
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: GATConv(h, h // heads, heads=heads, concat=True))

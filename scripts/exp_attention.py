@@ -1,0 +1,136 @@
+"""Products and softmax with per-call edge values on the Reddit-shaped graph (h = 256, FLT32), one process, device events after a
+warm-up.  JSON lines:
+  spmm_values with heads = 1 and heads = 8 (time, gather rate: every stored entry reads one X row of h * 4 bytes), next to
+    (a) the only other way to apply new values: free the group, create it again with the new values, mul -- per step, host clock;
+    (b) pygim_sddmm on the same graph (it gathers a G row and an X row per entry where spmm_values gathers the X row);
+    (c) the frozen-values product mul: the code stream, and the sweep (lds_mode = 2);
+  edge_softmax forward and backward at heads = 8 (time, bytes moved / time) next to the torch composite (index_reduce_ amax, exp,
+    index_add_, divide);
+  the bytes both *_workspace functions return for this shape.
+    python scripts/exp_attention.py [--iters 10]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from pygim_amd import _lib, attention, autograd, pim_ops, synth  # noqa: E402
+from pygim_amd.backend_pim import spmm as spmm_mod  # noqa: E402
+from pygim_amd.sparse_tensor import SparseTensorShim  # noqa: E402
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--h", type=int, default=256)
+    ap.add_argument("--shape", default="reddit")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    n, nnz, d_max = synth.SHAPES[args.shape]
+    h, iters = args.h, args.iters
+    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    g = attention.EdgeGraph(rowptr, col, (n, n))
+    x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform")
+    gen = torch.Generator(device=dev).manual_seed(1)
+    gathered = nnz * h * 4
+
+    def line(**kw):
+        print(json.dumps({"graph": args.shape, "h": h, "nnz": nnz, **kw}), flush=True)
+
+    # ---- spmm_values, alternating with pygim_sddmm (two rounds: the spread) ----
+    v1 = torch.rand(nnz, 1, device=dev, generator=gen)
+    v8 = torch.rand(nnz, 8, device=dev, generator=gen)
+    gr = synth.features(n, h, torch.float32, seed=1, device=dev, kind="uniform")
+    for rnd in range(2):
+        t1 = timed(lambda: attention._run_spmm_values(g, v1, x, 1), iters)
+        sd = timed(lambda: autograd.sddmm(g.rowptr, g.col, gr, x), iters)
+        t8 = timed(lambda: attention._run_spmm_values(g, v8, x, 8), iters)
+        line(what="spmm_values vs sddmm", round=rnd, spmm_values_heads1_ms=round(t1, 3), spmm_values_heads8_ms=round(t8, 3), sddmm_ms=round(sd, 3),
+             heads1_gather_tb_s=round(gathered / t1 / 1e9, 2), heads8_gather_tb_s=round(gathered / t8 / 1e9, 2),
+             sddmm_x_gather_tb_s=round(gathered / sd / 1e9, 2))
+    del gr, v8
+    line(what="workspace bytes", spmm_values=_lib.spmm_values_workspace(_lib.FLT32, n, nnz, h, 8),
+         edge_softmax_heads8=_lib.edge_softmax_workspace(_lib.FLT32, n, nnz, 8))
+
+    # ---- edge_softmax forward / backward at heads = 8 against the torch composite ----
+    heads = 8
+    s = torch.randn(nnz, heads, device=dev, generator=gen) * 3
+    dP = torch.randn(nnz, heads, device=dev, generator=gen)
+    row = g.row.long()
+    P = attention._run_edge_softmax(g, s, None, heads)
+    fwd = timed(lambda: attention._run_edge_softmax(g, s, None, heads), iters)
+    bwd = timed(lambda: attention._run_edge_softmax(g, P, dP, heads), iters)
+
+    def torch_fwd():
+        m = torch.full((n, heads), -float("inf"), device=dev).index_reduce_(0, row, s, "amax", include_self=True)
+        e = torch.exp(s - m[row])
+        return e / torch.zeros(n, heads, device=dev).index_add_(0, row, e)[row]
+
+    def torch_bwd():
+        t = torch.zeros(n, heads, device=dev).index_add_(0, row, P * dP)
+        return P * (dP - t[row])
+
+    tf, tb = timed(torch_fwd, max(2, iters // 3)), timed(torch_bwd, max(2, iters // 3))
+    elems = nnz * heads * 4
+    line(what="edge_softmax heads=8", forward_ms=round(fwd, 3), backward_ms=round(bwd, 3), torch_forward_ms=round(tf, 3), torch_backward_ms=round(tb, 3),
+         forward_min_bytes_tb_s=round(2 * elems / fwd / 1e9, 2), backward_min_bytes_tb_s=round(3 * elems / bwd / 1e9, 2),
+         note="rates count one read of every input and one write; rows longer than a 64-entry batch are read twice")
+    del s, dP, P, row
+
+    # ---- (a) new values through a new group, (c) the frozen-values product ----
+    val = v1[:, 0].contiguous()
+    adj = SparseTensorShim(rowptr=rowptr.long(), col=col.long(), value=val, sparse_sizes=(n, n))
+
+    def regroup_step(A):
+        A.free_group()
+        A.csr = []
+        A.to_pim_group_csr(h, 1)
+        return A.mul(x)
+
+    A = spmm_mod.SparseTensorCOO(adj, dtype=torch.float32, format="CSR")
+    A.to_pim_group_csr(h, 1)
+    ref = A.mul(x)
+    got = attention._run_spmm_values(g, v1, x, 1)
+    agree = bool(torch.allclose(got, ref, rtol=1e-4, atol=1e-3))
+    torch.cuda.synchronize()
+    steps = 3
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        regroup_step(A)
+    torch.cuda.synchronize()
+    regroup_ms = (time.perf_counter() - t0) * 1e3 / steps
+    t1 = timed(lambda: attention._run_spmm_values(g, v1, x, 1), iters)
+    mul_code = timed(lambda: A.mul(x), iters)
+    note = _lib.group_lds_note(A.sp_info_ptr)
+    A.free_group()
+    old = _lib.set_tunable("lds_mode", 2)
+    A.csr = []
+    A.to_pim_group_csr(h, 1)
+    mul_sweep = timed(lambda: A.mul(x), iters)
+    A.free_group()
+    _lib.set_tunable("lds_mode", old)
+    line(what="new values per step", regroup_then_mul_ms=round(regroup_ms, 2), spmm_values_heads1_ms=round(t1, 3), ratio=round(regroup_ms / t1, 2),
+         same_product=agree, frozen_mul_ms=round(mul_code, 3), frozen_mul_form=note[:120], frozen_mul_sweep_ms=round(mul_sweep, 3))
+    torch.ops.pim_ops.dpu_release()
+
+
+if __name__ == "__main__":
+    main()
