@@ -236,6 +236,36 @@ int pygim_edge_softmax(int dtype, int64_t nrows, const int32_t *rowptr, int64_t 
 int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *P, const void *dP,
                                 int64_t heads, void *out, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
+ *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1
+ *     when values is NULL.  The contract of pygim_spmm_values: device pointers only, a valid CSR guaranteed by the caller, nnz = 0,
+ *     empty rows and any h >= 1 allowed, row strides ldx, ldo >= h, work is only enqueued on `stream`, scratch from the caller
+ *     (pygim_spmm_reduce_workspace bytes: a function of its arguments alone, -1 for bad arguments; 16-byte aligned), no atomics, the
+ *     same bits on every launch.  Empty rows store 0.
+ *     MEAN (FLT32 / DBL64): the sum of pygim_spmm_values, in its order and within its bound, divided by the row's number of stored
+ *       entries (duplicates count separately; not the sum of the values).  arg must be NULL.
+ *     MAX / MIN (all six types): integers compare as signed values of their type and the integer product wraps like the type's own
+ *       arithmetic; a float result is exactly one of the products.  arg, when not NULL ([nrows, h] int32, contiguous), receives the
+ *       index in stored order of the entry that won, -1 for empty rows.  Among equal products the LOWEST entry index wins (-0.0 and
+ *       +0.0 are equal).  A NaN product never wins against a number, wherever it stands in the row; a row whose products are all NaN
+ *       stores NaN and arg -1.
+ *   pygim_spmm_reduce_backward (FLT32 / DBL64): the gradient of MAX / MIN with respect to X, as a gather on the transposed structure:
+ *       dX[c, f] = sum over the entries e' of row c of A^T, in order, of (arg[r, f] == e ? w[e] * G[r, f] : 0),  e = perm[e'], r = rows_t[e']
+ *     rowptr_t [ncols + 1], rows_t [nnz] (the A-row of every entry of A^T) and perm [nnz] (its index in A: the stable sort of A's
+ *     entries by column) describe A^T; values are in A's order or NULL; arg is the forward's.  dX[0:ncols, 0:h] (row stride ldd) is
+ *     overwritten; every output row has one owner.  Within 1e-5 (FLT32) / 1e-12 (DBL64) of sum |w . G| of the exact value.
+ *   PYGIM_ERR_INVALID: an unknown op, an integer type with MEAN or with the backward, arg with MEAN, a workspace that is too small. */
+#define PYGIM_REDUCE_MEAN 1
+#define PYGIM_REDUCE_MAX 2
+#define PYGIM_REDUCE_MIN 3
+int64_t pygim_spmm_reduce_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h);
+int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                      const void *values /* [nnz] or NULL */, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo,
+                      int32_t *arg /* [nrows, h] or NULL; max / min only */, void *workspace, int64_t workspace_bytes, void *stream);
+int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t, const int32_t *rows_t, const int32_t *perm,
+                               int64_t nnz, const void *values /* A's order, or NULL */, const void *G, int64_t ldg,
+                               const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream);
+
 /* ---- introspection -----------------------------------------------------------
  * Milliseconds of the last host-pointer run, in the reference's Timer buckets
  * (support/timer.h; printed as [DATA] lines, spmm_mul_csr.c:563-580):

@@ -22,11 +22,13 @@ EXPORTS = [
     "pygim_group_lds_tiles", "pygim_group_lds_runs", "pygim_group_serial", "pygim_group_host_windows",
     "pygim_group_create_transposed", "pygim_sddmm",
     "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
+    "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
 INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
 CSR, COO = 0, 1
+REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
 
 
 class PygimError(RuntimeError):
@@ -69,6 +71,10 @@ def lib():
         L.pygim_edge_softmax_backward.argtypes = [c_int, c_i64, vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_edge_softmax_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
         L.pygim_edge_softmax_workspace.restype = c_i64
+        L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_reduce_workspace.restype = c_i64
+        L.pygim_spmm_reduce_backward.argtypes = [c_int, c_i64, vp, vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -218,6 +224,27 @@ def edge_softmax_backward(dtype, nrows, rowptr_ptr, nnz, p_ptr, dp_ptr, heads, o
     """out = P * (dP - sum_row P * dP): the gradient of edge_softmax with respect to the scores"""
     check(lib().pygim_edge_softmax_backward(int(dtype), int(nrows), _vp(rowptr_ptr), int(nnz), _vp(p_ptr), _vp(dp_ptr), int(heads),
                                             _vp(out_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def spmm_reduce_workspace(dtype, op, nrows, nnz, h):
+    """bytes of scratch spmm_reduce needs for this type, reduction and shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_reduce_workspace(int(dtype), int(op), int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_reduce_workspace arguments")
+    return n
+
+
+def spmm_reduce(dtype, op, nrows, rowptr_ptr, col_ptr, nnz, val_ptr, x_ptr, ldx, h, out_ptr, ldo, arg_ptr, ws_ptr, ws_bytes, stream=0):
+    """out[r, f] = mean / max / min over the entries e of row r of values[e] * X[col[e], f] (REDUCE_*; val_ptr 0: unit weights;
+    arg_ptr: int32 [nrows, h] for the winning entry of max / min, or 0)"""
+    check(lib().pygim_spmm_reduce(int(dtype), int(op), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(val_ptr), _vp(x_ptr), int(ldx),
+                                  int(h), _vp(out_ptr), int(ldo), _vp(arg_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def spmm_reduce_backward(dtype, ncols, rowptr_t_ptr, rows_t_ptr, perm_ptr, nnz, val_ptr, g_ptr, ldg, arg_ptr, h, dx_ptr, ldd, stream=0):
+    """dX[c] = sum over the entries of row c of A^T of (arg[r] == e ? values[e] * G[r] : 0): the gradient of max / min (FLT32 / DBL64)"""
+    check(lib().pygim_spmm_reduce_backward(int(dtype), int(ncols), _vp(rowptr_t_ptr), _vp(rows_t_ptr), _vp(perm_ptr), int(nnz), _vp(val_ptr),
+                                           _vp(g_ptr), int(ldg), _vp(arg_ptr), int(h), _vp(dx_ptr), int(ldd), _vp(stream)))
 
 
 def group_free(handle):

@@ -195,6 +195,15 @@ class SparseGroupBase:
 
         return spmm_values(EdgeGraph.of(self), value, B, heads)
 
+    # -- mean / max / min over a row's stored entries (pygim_amd/reduce.py) --------------------------------------
+    def mul_reduce(self, B: torch.Tensor, reduce: str):
+        """``torch_sparse.matmul(self.raw, B, reduce)`` for ``"mean"``, ``"max"`` or ``"min"`` on the raw tensor's structure, weighted
+        by its stored values (cast to B's dtype) when it has them and by ones otherwise.  A reduction other than the sum cannot be
+        compiled into a group: none is created or used.  Differentiable in B (float32 / float64)."""
+        from ..reduce import matmul_reduce
+
+        return matmul_reduce(self, B, reduce)
+
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):
         assert nparts > 0

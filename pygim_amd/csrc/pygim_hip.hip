@@ -25,6 +25,7 @@
 #include "sddmm_dev.hpp"
 #include "spmm_values_dev.hpp"
 #include "edge_softmax_dev.hpp"
+#include "spmm_reduce_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -689,6 +690,82 @@ int pygim_edge_softmax(int dtype, int64_t nrows, const int32_t *rowptr, int64_t 
 int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *P, const void *dP, int64_t heads, void *out,
                                 void *workspace, int64_t workspace_bytes, void *stream) {
     return edge_softmax_call(ES_BACKWARD, dtype, nrows, rowptr, nnz, P, dP, heads, out, workspace, workspace_bytes, stream);
+}
+
+// ---- mean / max / min over a row's stored entries, and the gradient of max / min (spmm_reduce_dev.hpp) ----
+static size_t reduce_elem_bytes(int dtype) {
+    switch (dtype) {
+        case PYGIM_INT8: return 1;
+        case PYGIM_INT16: return 2;
+        case PYGIM_INT32: case PYGIM_FLT32: return 4;
+        case PYGIM_INT64: case PYGIM_DBL64: return 8;
+        default: return 0;
+    }
+}
+
+int64_t pygim_spmm_reduce_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
+    const size_t elem = reduce_elem_bytes(dtype);
+    if (elem == 0 || (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)) return -1;
+    if (op == PYGIM_REDUCE_MEAN && dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return -1;
+    if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll) return -1;
+    return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, elem);
+}
+
+int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, const void *X,
+                      int64_t ldx, int64_t h, void *out, int64_t ldo, int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (reduce_elem_bytes(dtype) == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: unknown element type");
+    if (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)
+        return fail(PYGIM_ERR_INVALID, "spmm_reduce: op must be PYGIM_REDUCE_MEAN, _MAX or _MIN (sums: pygim_spmm_values, pygim_spmm_run_group)");
+    if (op == PYGIM_REDUCE_MEAN && dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64)
+        return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean needs FLT32 or DBL64");
+    if (op == PYGIM_REDUCE_MEAN && arg) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean has no arg output");
+    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldx < h || ldo < h)
+        return fail(PYGIM_ERR_INVALID, "bad spmm_reduce sizes / strides");
+    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: entries without rows");
+    if (!rowptr || (nrows > 0 && !out) || (nnz > 0 && (!colind || !X))) return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / X / out");
+    if (!is_device_ptr(rowptr) || (nrows > 0 && (!is_device_ptr(out) || (arg && !is_device_ptr(arg)))) ||
+        (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(X) || (values && !is_device_ptr(values)))))
+        return fail(PYGIM_ERR_INVALID, "pygim_spmm_reduce needs device pointers");
+    if (arg && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: arg must be 4-byte aligned");
+    const int64_t need = pygim_spmm_reduce_workspace(dtype, op, nrows, nnz, h);
+    if (need > 0 && (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace)))
+        return fail(PYGIM_ERR_INVALID, "spmm_reduce: workspace too small, misaligned or not device memory (pygim_spmm_reduce_workspace)");
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case PYGIM_INT8: launch_spmm_reduce_op<int8_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+        case PYGIM_INT16: launch_spmm_reduce_op<int16_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+        case PYGIM_INT32: launch_spmm_reduce_op<int32_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+        case PYGIM_INT64: launch_spmm_reduce_op<int64_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+        case PYGIM_FLT32: launch_spmm_reduce_op<float>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+        default: launch_spmm_reduce_op<double>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t, const int32_t *rows_t, const int32_t *perm, int64_t nnz,
+                               const void *values, const void *G, int64_t ldg, const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: type must be FLT32 or DBL64");
+    if (ncols < 0 || ncols >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldg < h || ldd < h)
+        return fail(PYGIM_ERR_INVALID, "bad spmm_reduce_backward sizes / strides");
+    if (nnz > 0 && ncols == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: entries without columns");
+    if (!rowptr_t || (ncols > 0 && !dX) || (nnz > 0 && (!rows_t || !perm || !G || !arg)))
+        return fail(PYGIM_ERR_INVALID, "bad rowptr_t / rows_t / perm / G / arg / dX");
+    if (!is_device_ptr(rowptr_t) || (ncols > 0 && !is_device_ptr(dX)) ||
+        (nnz > 0 && (!is_device_ptr(rows_t) || !is_device_ptr(perm) || !is_device_ptr(G) || !is_device_ptr(arg) || (values && !is_device_ptr(values)))))
+        return fail(PYGIM_ERR_INVALID, "pygim_spmm_reduce_backward needs device pointers");
+    if (nnz > 0 && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: arg must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PYGIM_FLT32)
+        launch_spmm_reduce_bwd<float>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, perm, (uint32_t)ncols, (const float *)values, (const float *)G,
+                                      (uint64_t)ldg, arg, (uint32_t)h, (float *)dX, (uint64_t)ldd, st);
+    else
+        launch_spmm_reduce_bwd<double>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, perm, (uint32_t)ncols, (const double *)values, (const double *)G,
+                                       (uint64_t)ldg, arg, (uint32_t)h, (double *)dX, (uint64_t)ldd, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int pygim_group_timers(int64_t handle, double out_ms[5]) {

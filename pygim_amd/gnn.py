@@ -6,7 +6,7 @@ pyg_sage_conv.py:122-155), written on plain torch.nn (torch_geometric is not ins
 
     Linear -> BN -> ReLU -> [conv -> BN -> ReLU] x L -> Linear          (dropout is identity in eval)
     GCNConv : lin(x) (no bias) -> aggregate -> + bias        (no degree normalisation in the reference)
-    SAGEConv: lin_l(aggregate(x)) + lin_r(x)                  (sum aggregation through adj_t.mul)
+    SAGEConv: lin_l(aggregate(x)) + lin_r(x)                  (sum aggregation through adj_t.mul; aggr="mean" / "max": spmm_reduce)
     GINConv : nn((1 + eps) * x + aggregate(x)),  nn = Linear -> BN -> ReLU -> Linear  (PyG MLP([h, h, h]))
 with aggregate = quantise -> adj_t.mul -> dequantise (pygim_amd/quantize.py).  ``adj_t`` is a
 SparseTensor (cpu path), a backend_pim SparseTensorCOO, or a pygim_amd.dist.RowShardAdj (multi-GPU:
@@ -34,13 +34,25 @@ class GCNConv(torch.nn.Module):
 
 
 class SAGEConv(torch.nn.Module):
-    def __init__(self, in_channels, out_channels, bias=True, **_):
+    """``aggr="sum"``: the reference's layer (quantise -> adj_t.mul -> dequantise).  ``"mean"`` / ``"max"`` / ``"min"``: PyG's other
+    aggregators through pygim_amd.reduce on the adjacency's plain CSR: float32 / float64, trainable, no quantisation, one GPU."""
+
+    def __init__(self, in_channels, out_channels, bias=True, aggr="sum", **_):
         super().__init__()
+        if aggr not in ("sum", "add", "mean", "max", "min"):
+            raise ValueError(f"SAGEConv: aggr must be 'sum', 'mean', 'max' or 'min', got {aggr!r}")
+        self.aggr = "sum" if aggr == "add" else aggr
         self.lin_l = Linear(in_channels, out_channels, bias=bias)
         self.lin_r = Linear(in_channels, out_channels, bias=False)
 
     def forward(self, x, adj_t):
-        return self.lin_l(message_and_aggregate(adj_t, x)) + self.lin_r(x)
+        if self.aggr == "sum":
+            return self.lin_l(message_and_aggregate(adj_t, x)) + self.lin_r(x)
+        if getattr(adj_t, "row_sharded", False):
+            raise NotImplementedError(f"SAGEConv: aggr={self.aggr!r} is not available on a RowShardAdj (one GPU only); use aggr='sum'")
+        from .reduce import matmul_reduce
+
+        return self.lin_l(matmul_reduce(adj_t, x, self.aggr)) + self.lin_r(x)
 
 
 class GINConv(torch.nn.Module):
@@ -126,8 +138,8 @@ class GCN(_Stack):
 
 
 class SAGE(_Stack):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5):
-        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout, lambda h: SAGEConv(h, h))
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, aggr="sum"):
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout, lambda h: SAGEConv(h, h, aggr=aggr))
 
 
 class GIN(_Stack):

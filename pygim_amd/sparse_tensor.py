@@ -165,11 +165,34 @@ class SparseTensorShim:
         return f"SparseTensorShim(sizes={self._sizes}, nnz={self.nnz()}, value={'yes' if self.has_value() else 'none'})"
 
 
+def _shim_reduce(src, other, reduce: str):
+    """``torch_sparse.matmul(src, other, reduce)`` for mean / max / min: one message ``value[e] * other[col[e]]`` per stored entry
+    (duplicates are separate entries; integer products wrap like the type), reduced per row.  Empty rows give 0.  Mean divides the sum
+    by the row's number of stored entries, not by the sum of its values (integers: floor division, as torch_scatter does)."""
+    row, col, value = src.coo()
+    n = src.size(0)
+    msg = other.index_select(0, col.to(other.device))
+    if value is not None:
+        msg = value.to(other.device, other.dtype).unsqueeze(1) * msg
+    row = row.to(other.device)
+    out = torch.zeros((n, other.size(1)), dtype=other.dtype, device=other.device)
+    if reduce == "mean":
+        out = out.index_add(0, row, msg)
+        count = torch.bincount(row, minlength=n).clamp_(min=1).unsqueeze(1)
+        return out / count.to(other.dtype) if other.is_floating_point() else torch.div(out, count, rounding_mode="floor").to(other.dtype)
+    if msg.size(0) == 0:
+        return out
+    return out.scatter_reduce(0, row.unsqueeze(1).expand_as(msg), msg, "amax" if reduce == "max" else "amin", include_self=False)
+
+
 def _shim_matmul(src, other, reduce: str = "sum"):
     """``torch_sparse.matmul`` stand-in for the version=cpu path: torch's own COO kernel.
 
-    Sum-reduce only (the reference's call sites use the default, spmm_test.py:25).
+    The reference's call sites use the default sum (spmm_test.py:25); ``"mean"``, ``"max"`` and ``"min"`` are plain torch ops on the
+    CSR with torch_sparse's semantics (``_shim_reduce``).
     """
+    if reduce in ("mean", "max", "min"):
+        return _shim_reduce(src, other, reduce)
     assert reduce in ("sum", "add")
     if other.is_floating_point() and not other.is_cuda:
         # floats: torch's CSR x dense kernel (MKL, all cores) -- about 20x faster than the COO path on the

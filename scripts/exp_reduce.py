@@ -1,0 +1,109 @@
+"""Mean / max / min aggregation on the Reddit-shaped graph (h = 256, FLT32), one process, device events after a warm-up.  JSON lines:
+  spmm_reduce mean, max without arg and max with arg next to spmm_values with one head in the same run (time, gather rate: every
+    stored entry reads one X row of h * 4 bytes), two rounds: the spread;
+  the gradient of max with respect to X (pygim_spmm_reduce_backward: an arg row beside every G row);
+  the torch composite for scale: index_reduce_ amax over the per-entry messages, in blocks of 2^23 entries (the messages of the whole
+    graph would be 117 GB);
+  the bytes pygim_spmm_reduce_workspace returns for this shape.
+    python scripts/exp_reduce.py [--iters 10]"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from pygim_amd import _lib, attention, pim_ops, reduce as red, synth  # noqa: E402
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--h", type=int, default=256)
+    ap.add_argument("--shape", default="reddit")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    n, nnz, d_max = synth.SHAPES[args.shape]
+    h, iters = args.h, args.iters
+    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    g = attention.EdgeGraph(rowptr, col, (n, n))
+    x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform")
+    gen = torch.Generator(device=dev).manual_seed(1)
+    gathered = nnz * h * 4
+
+    def line(**kw):
+        print(json.dumps({"graph": args.shape, "h": h, "nnz": nnz, **kw}), flush=True)
+
+    v1 = torch.rand(nnz, 1, device=dev, generator=gen)
+    w = v1[:, 0].contiguous()
+    MEAN, MAX = red.REDUCE_CODE["mean"], red.REDUCE_CODE["max"]
+    for rnd in range(2):
+        sv = timed(lambda: attention._run_spmm_values(g, v1, x, 1), iters)
+        mean = timed(lambda: red._run_spmm_reduce(g, w, x, MEAN, False), iters)
+        mx = timed(lambda: red._run_spmm_reduce(g, w, x, MAX, False), iters)
+        mxa = timed(lambda: red._run_spmm_reduce(g, w, x, MAX, True), iters)
+        mx1 = timed(lambda: red._run_spmm_reduce(g, None, x, MAX, True), iters)
+        line(what="spmm_reduce vs spmm_values", round=rnd, spmm_values_heads1_ms=round(sv, 3), mean_ms=round(mean, 3), max_ms=round(mx, 3),
+             max_arg_ms=round(mxa, 3), max_arg_unit_weights_ms=round(mx1, 3), mean_over_values=round(mean / sv, 3), max_over_values=round(mx / sv, 3),
+             max_arg_over_values=round(mxa / sv, 3), max_arg_gather_tb_s=round(gathered / mxa / 1e9, 2))
+    line(what="workspace bytes", mean=_lib.spmm_reduce_workspace(_lib.FLT32, MEAN, n, nnz, h), max=_lib.spmm_reduce_workspace(_lib.FLT32, MAX, n, nnz, h))
+
+    # ---- the gradient of max with respect to X ----
+    out, arg = red._run_spmm_reduce(g, w, x, MAX, True)
+    gt, perm32 = red._transposed32(g)
+    G = synth.features(n, h, torch.float32, seed=1, device=dev, kind="uniform")
+    dX = torch.empty((n, h), device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def bwd():
+        _lib.spmm_reduce_backward(_lib.FLT32, n, gt.rowptr.data_ptr(), gt.col.data_ptr(), perm32.data_ptr(), nnz, w.data_ptr(), G.data_ptr(), h,
+                                  arg.data_ptr(), h, dX.data_ptr(), h, st)
+
+    for rnd in range(2):
+        sv = timed(lambda: attention._run_spmm_values(g, v1, x, 1), iters)
+        tb = timed(bwd, iters)
+        line(what="max backward", round=rnd, backward_ms=round(tb, 3), spmm_values_heads1_ms=round(sv, 3), backward_over_values=round(tb / sv, 3),
+             gather_tb_s=round(2 * gathered / tb / 1e9, 2), note="the rate counts a G row and an arg row per stored entry")
+    # every (row, feature) of a non-empty row has exactly one winner: the column sums of dX and of the rows' G * w[arg] agree
+    won = torch.gather(w, 0, arg.clamp(min=0).long().reshape(-1)).reshape(n, h) * (arg >= 0)
+    line(what="max backward check", sum_dx=float(dX.double().sum()), sum_w_g=float((won.double() * G.double()).sum()))
+    del dX, G, won
+
+    # ---- the torch composite ----
+    row = g.row.long()
+    colL = g.col.long()
+    step = 1 << 23
+
+    def composite():
+        o = torch.full((n, h), -float("inf"), device=dev)
+        for s in range(0, nnz, step):
+            o.index_reduce_(0, row[s:s + step], w[s:s + step].unsqueeze(1) * x[colL[s:s + step]], "amax", include_self=True)
+        return o
+
+    tc = timed(composite, 1)
+    comp = composite()
+    same = bool(torch.equal(torch.where(torch.isinf(comp), torch.zeros_like(out), comp), out))
+    del comp
+    mxa = timed(lambda: red._run_spmm_reduce(g, w, x, MAX, True), iters)
+    line(what="torch composite", index_reduce_amax_ms=round(tc, 2), max_arg_ms=round(mxa, 3), ratio=round(tc / mxa, 1), same_result=same)
+    torch.ops.pim_ops.dpu_release()
+
+
+if __name__ == "__main__":
+    main()
