@@ -23,7 +23,7 @@
 #endif
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
-#include "spmm_values_dev.hpp"
+#include "row_gather_dev.hpp"
 #include "edge_softmax_dev.hpp"
 #include "spmm_reduce_dev.hpp"
 #include <hsa/hsa.h>
@@ -591,65 +591,95 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
     }
 }
 
+}  // extern "C"
+
+// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, spmm_reduce and its backward ----
+// f(T()) with T the element type of `dtype` (the caller has checked it); INTS = false: FLT32 / DBL64 only
+template <bool INTS = false, typename F> static void with_elem_type(int dtype, F &&f) {
+    if constexpr (INTS) {
+        switch (dtype) {
+            case PYGIM_INT8: return f(int8_t());
+            case PYGIM_INT16: return f(int16_t());
+            case PYGIM_INT32: return f(int32_t());
+            case PYGIM_INT64: return f(int64_t());
+        }
+    }
+    if (dtype == PYGIM_FLT32) f(float());
+    else f(double());
+}
+
+static bool is_float_type(int dtype) { return dtype == PYGIM_FLT32 || dtype == PYGIM_DBL64; }
+
+// a pointer argument: checked when the call will use it (`used`: rows > 0, nnz > 0, ...) -- not null unless `optional`, and device memory
+struct PtrArg {
+    const void *p;
+    bool used, optional = false;
+};
+
+// the checks these entry points share, in their order; op names the entry point in the messages, `names` its pointers, ld0 / ld1 are
+// the two row strides, need_ws what pygim_<op>_workspace returns (<= 0: no workspace)
+static int check_csr_call(const char *op, const char *names, int64_t nrows, int64_t nnz, int64_t nnz_max, int64_t h, int64_t h_max, int64_t ld0, int64_t ld1,
+                          std::initializer_list<PtrArg> ptrs, int64_t need_ws = 0, const void *workspace = nullptr, int64_t workspace_bytes = 0) {
+    const std::string o(op);
+    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > nnz_max || h < 1 || h > h_max || ld0 < h || ld1 < h)
+        return fail(PYGIM_ERR_INVALID, "bad " + o + " sizes / strides");
+    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, o + ": entries without rows");
+    for (const PtrArg &a : ptrs)
+        if (a.used && !a.optional && !a.p) return fail(PYGIM_ERR_INVALID, std::string("bad ") + names);
+    for (const PtrArg &a : ptrs)
+        if (a.used && a.p && !is_device_ptr(a.p)) return fail(PYGIM_ERR_INVALID, "pygim_" + o + " needs device pointers");
+    if (need_ws > 0 && (!workspace || workspace_bytes < need_ws || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace)))
+        return fail(PYGIM_ERR_INVALID, o + ": workspace too small, misaligned or not device memory (pygim_" + o + "_workspace)");
+    return 0;
+}
+
+extern "C" {
+
 int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *G, int64_t ldg,
                 const void *X, int64_t ldx, int64_t h, void *out, void *stream) {
     if (int rc = need_init()) return rc;
-    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "sddmm: type must be FLT32 or DBL64");
-    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0xFFFFFFFFll - SD_EPW || h < 1 || h > 0xFFFFFFFFll || ldg < h || ldx < h)
-        return fail(PYGIM_ERR_INVALID, "bad sddmm sizes / strides");
-    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "sddmm: entries without rows");
-    if (!rowptr || (nnz > 0 && (!colind || !G || !X || !out))) return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / G / X / out");
-    if (!is_device_ptr(rowptr) || (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(G) || !is_device_ptr(X) || !is_device_ptr(out))))
-        return fail(PYGIM_ERR_INVALID, "pygim_sddmm needs device pointers");
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "sddmm: type must be FLT32 or DBL64");
+    if (int rc = check_csr_call("sddmm", "rowptr / colind / G / X / out", nrows, nnz, 0xFFFFFFFFll - SD_EPW, h, 0xFFFFFFFFll, ldg, ldx,
+                                {{rowptr, true}, {colind, nnz > 0}, {G, nnz > 0}, {X, nnz > 0}, {out, nnz > 0}}))
+        return rc;
     if (nnz == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PYGIM_FLT32)
-        launch_sddmm<float>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const float *)G, (uint64_t)ldg,
-                            (const float *)X, (uint64_t)ldx, (uint32_t)h, (float *)out, st);
-    else
-        launch_sddmm<double>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const double *)G, (uint64_t)ldg,
-                             (const double *)X, (uint64_t)ldx, (uint32_t)h, (double *)out, st);
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_sddmm<T>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)G, (uint64_t)ldg, (const T *)X,
+                        (uint64_t)ldx, (uint32_t)h, (T *)out, (hipStream_t)stream);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// ---- products and softmax with per-call edge values (spmm_values_dev.hpp, edge_softmax_dev.hpp) ----
 int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
     (void)heads;
-    if ((dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) || nnz < 0 || h < 1) return -1;
-    return (int64_t)spmm_values_workspace_bytes((uint64_t)nnz, (uint64_t)h, dtype == PYGIM_FLT32 ? 4 : 8);
+    if (!is_float_type(dtype) || nnz < 0 || h < 1) return -1;
+    return (int64_t)row_gather_slot_bytes((uint64_t)nnz, (uint64_t)h, dtype_size(dtype));
 }
 
 int64_t pygim_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t heads) {
     (void)nrows;
-    if ((dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) || nnz < 0 || heads < 1) return -1;
-    return (int64_t)edge_softmax_workspace_bytes((uint64_t)nnz, (uint64_t)heads, dtype == PYGIM_FLT32 ? 4 : 8);
+    if (!is_float_type(dtype) || nnz < 0 || heads < 1) return -1;
+    return (int64_t)edge_softmax_workspace_bytes((uint64_t)nnz, (uint64_t)heads, dtype_size(dtype));
 }
 
 int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, int64_t heads,
                       const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32 or DBL64");
-    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldx < h || ldo < h)
-        return fail(PYGIM_ERR_INVALID, "bad spmm_values sizes / strides");
-    if (heads < 1 || h % heads != 0) return fail(PYGIM_ERR_INVALID, "spmm_values: heads must divide h");
-    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "spmm_values: entries without rows");
-    if (!rowptr || (nrows > 0 && !out) || (nnz > 0 && (!colind || !values || !X)))
-        return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / values / X / out");
-    if (!is_device_ptr(rowptr) || (nrows > 0 && !is_device_ptr(out)) ||
-        (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(values) || !is_device_ptr(X))))
-        return fail(PYGIM_ERR_INVALID, "pygim_spmm_values needs device pointers");
-    const int64_t need = pygim_spmm_values_workspace(dtype, nrows, nnz, h, heads);
-    if (need > 0 && (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace)))
-        return fail(PYGIM_ERR_INVALID, "spmm_values: workspace too small, misaligned or not device memory (pygim_spmm_values_workspace)");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PYGIM_FLT32)
-        launch_spmm_values<float>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const float *)values, (uint32_t)heads,
-                                  (const float *)X, (uint64_t)ldx, (uint32_t)h, (float *)out, (uint64_t)ldo, (float *)workspace, st);
-    else
-        launch_spmm_values<double>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const double *)values,
-                                   (uint32_t)heads, (const double *)X, (uint64_t)ldx, (uint32_t)h, (double *)out, (uint64_t)ldo, (double *)workspace, st);
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32 or DBL64");
+    if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "spmm_values: heads must divide h");
+    if (int rc = check_csr_call("spmm_values", "rowptr / colind / values / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {colind, nnz > 0}, {values, nnz > 0}, {X, nnz > 0}},
+                                pygim_spmm_values_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
+        return rc;
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_row_gather<T, FoldSum<false>>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values,
+                                             (uint32_t)heads, (const T *)X, (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, nullptr, workspace,
+                                             (hipStream_t)stream);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -657,7 +687,7 @@ int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int
 static int edge_softmax_call(int mode, int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *a, const void *b, int64_t heads, void *out,
                              void *workspace, int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "edge_softmax: type must be FLT32 or DBL64");
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "edge_softmax: type must be FLT32 or DBL64");
     if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || heads < 1 || heads > 0x7FFFFFFFll)
         return fail(PYGIM_ERR_INVALID, "bad edge_softmax sizes");
     if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "edge_softmax: entries without rows");
@@ -671,13 +701,11 @@ static int edge_softmax_call(int mode, int dtype, int64_t nrows, const int32_t *
         return fail(PYGIM_ERR_INVALID, "edge_softmax: workspace too small, misaligned or not device memory (pygim_edge_softmax_workspace)");
     hipStream_t st = (hipStream_t)stream;
     const uint32_t *rp = (const uint32_t *)rowptr;
-    if (dtype == PYGIM_FLT32) {
-        if (bwd) launch_edge_softmax<float, ES_BACKWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const float *)a, (const float *)b, (uint32_t)heads, (float *)out, workspace, st);
-        else launch_edge_softmax<float, ES_FORWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const float *)a, nullptr, (uint32_t)heads, (float *)out, workspace, st);
-    } else {
-        if (bwd) launch_edge_softmax<double, ES_BACKWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const double *)a, (const double *)b, (uint32_t)heads, (double *)out, workspace, st);
-        else launch_edge_softmax<double, ES_FORWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const double *)a, nullptr, (uint32_t)heads, (double *)out, workspace, st);
-    }
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (bwd) launch_edge_softmax<T, ES_BACKWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const T *)a, (const T *)b, (uint32_t)heads, (T *)out, workspace, st);
+        else launch_edge_softmax<T, ES_FORWARD>(rp, (uint32_t)nrows, (uint32_t)nnz, (const T *)a, nullptr, (uint32_t)heads, (T *)out, workspace, st);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -692,54 +720,31 @@ int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr,
     return edge_softmax_call(ES_BACKWARD, dtype, nrows, rowptr, nnz, P, dP, heads, out, workspace, workspace_bytes, stream);
 }
 
-// ---- mean / max / min over a row's stored entries, and the gradient of max / min (spmm_reduce_dev.hpp) ----
-static size_t reduce_elem_bytes(int dtype) {
-    switch (dtype) {
-        case PYGIM_INT8: return 1;
-        case PYGIM_INT16: return 2;
-        case PYGIM_INT32: case PYGIM_FLT32: return 4;
-        case PYGIM_INT64: case PYGIM_DBL64: return 8;
-        default: return 0;
-    }
-}
-
 int64_t pygim_spmm_reduce_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
-    const size_t elem = reduce_elem_bytes(dtype);
-    if (elem == 0 || (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)) return -1;
-    if (op == PYGIM_REDUCE_MEAN && dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return -1;
+    if (dtype_size(dtype) == 0 || (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)) return -1;
+    if (op == PYGIM_REDUCE_MEAN && !is_float_type(dtype)) return -1;
     if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll) return -1;
-    return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, elem);
+    return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, dtype_size(dtype));
 }
 
 int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, const void *X,
                       int64_t ldx, int64_t h, void *out, int64_t ldo, int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (reduce_elem_bytes(dtype) == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: unknown element type");
+    if (dtype_size(dtype) == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: unknown element type");
     if (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)
         return fail(PYGIM_ERR_INVALID, "spmm_reduce: op must be PYGIM_REDUCE_MEAN, _MAX or _MIN (sums: pygim_spmm_values, pygim_spmm_run_group)");
-    if (op == PYGIM_REDUCE_MEAN && dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64)
-        return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean needs FLT32 or DBL64");
+    if (op == PYGIM_REDUCE_MEAN && !is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean needs FLT32 or DBL64");
     if (op == PYGIM_REDUCE_MEAN && arg) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean has no arg output");
-    if (nrows < 0 || nrows >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldx < h || ldo < h)
-        return fail(PYGIM_ERR_INVALID, "bad spmm_reduce sizes / strides");
-    if (nnz > 0 && nrows == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: entries without rows");
-    if (!rowptr || (nrows > 0 && !out) || (nnz > 0 && (!colind || !X))) return fail(PYGIM_ERR_INVALID, "bad rowptr / colind / X / out");
-    if (!is_device_ptr(rowptr) || (nrows > 0 && (!is_device_ptr(out) || (arg && !is_device_ptr(arg)))) ||
-        (nnz > 0 && (!is_device_ptr(colind) || !is_device_ptr(X) || (values && !is_device_ptr(values)))))
-        return fail(PYGIM_ERR_INVALID, "pygim_spmm_reduce needs device pointers");
     if (arg && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: arg must be 4-byte aligned");
-    const int64_t need = pygim_spmm_reduce_workspace(dtype, op, nrows, nnz, h);
-    if (need > 0 && (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0 || !is_device_ptr(workspace)))
-        return fail(PYGIM_ERR_INVALID, "spmm_reduce: workspace too small, misaligned or not device memory (pygim_spmm_reduce_workspace)");
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case PYGIM_INT8: launch_spmm_reduce_op<int8_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-        case PYGIM_INT16: launch_spmm_reduce_op<int16_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-        case PYGIM_INT32: launch_spmm_reduce_op<int32_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-        case PYGIM_INT64: launch_spmm_reduce_op<int64_t>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-        case PYGIM_FLT32: launch_spmm_reduce_op<float>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-        default: launch_spmm_reduce_op<double>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, values, X, (uint64_t)ldx, (uint32_t)h, out, (uint64_t)ldo, arg, workspace, st); break;
-    }
+    if (int rc = check_csr_call("spmm_reduce", "rowptr / colind / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {arg, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {values, nnz > 0, true}},
+                                pygim_spmm_reduce_workspace(dtype, op, nrows, nnz, h), workspace, workspace_bytes))
+        return rc;
+    with_elem_type<true>(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_spmm_reduce<T>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values, (const T *)X,
+                              (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, arg, workspace, (hipStream_t)stream);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -747,23 +752,16 @@ int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, c
 int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t, const int32_t *rows_t, const int32_t *perm, int64_t nnz,
                                const void *values, const void *G, int64_t ldg, const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream) {
     if (int rc = need_init()) return rc;
-    if (dtype != PYGIM_FLT32 && dtype != PYGIM_DBL64) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: type must be FLT32 or DBL64");
-    if (ncols < 0 || ncols >= 0xFFFFFFFFll || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll || ldg < h || ldd < h)
-        return fail(PYGIM_ERR_INVALID, "bad spmm_reduce_backward sizes / strides");
-    if (nnz > 0 && ncols == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: entries without columns");
-    if (!rowptr_t || (ncols > 0 && !dX) || (nnz > 0 && (!rows_t || !perm || !G || !arg)))
-        return fail(PYGIM_ERR_INVALID, "bad rowptr_t / rows_t / perm / G / arg / dX");
-    if (!is_device_ptr(rowptr_t) || (ncols > 0 && !is_device_ptr(dX)) ||
-        (nnz > 0 && (!is_device_ptr(rows_t) || !is_device_ptr(perm) || !is_device_ptr(G) || !is_device_ptr(arg) || (values && !is_device_ptr(values)))))
-        return fail(PYGIM_ERR_INVALID, "pygim_spmm_reduce_backward needs device pointers");
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: type must be FLT32 or DBL64");
+    if (int rc = check_csr_call("spmm_reduce_backward", "rowptr_t / rows_t / perm / G / arg / dX", ncols, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldg, ldd,
+                                {{rowptr_t, true}, {dX, ncols > 0}, {rows_t, nnz > 0}, {perm, nnz > 0}, {G, nnz > 0}, {arg, nnz > 0}, {values, nnz > 0, true}}))
+        return rc;
     if (nnz > 0 && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: arg must be 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PYGIM_FLT32)
-        launch_spmm_reduce_bwd<float>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, perm, (uint32_t)ncols, (const float *)values, (const float *)G,
-                                      (uint64_t)ldg, arg, (uint32_t)h, (float *)dX, (uint64_t)ldd, st);
-    else
-        launch_spmm_reduce_bwd<double>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, perm, (uint32_t)ncols, (const double *)values, (const double *)G,
-                                       (uint64_t)ldg, arg, (uint32_t)h, (double *)dX, (uint64_t)ldd, st);
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_spmm_reduce_bwd<T>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, perm, (uint32_t)ncols, (const T *)values, (const T *)G, (uint64_t)ldg,
+                                  arg, (uint32_t)h, (T *)dX, (uint64_t)ldd, (hipStream_t)stream);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }

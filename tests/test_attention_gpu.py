@@ -78,6 +78,15 @@ def spmm_reference(n, rowptr, col, val, heads, X, h):
 @pytest.mark.parametrize("h", [1, 9, 32, 100, 256])
 @pytest.mark.parametrize("graph", ["small", "hub"])
 def test_spmm_values_parity(rng, dtype, h, graph):
+    check_spmm_values_parity(rng, dtype, h, graph)
+
+
+def test_spmm_values_parity_over_three_feature_chunks(rng):
+    """h = 300: the misaligned stride gives 300 one-element pieces, three blockIdx.y chunks of 128, the last one partly empty"""
+    check_spmm_values_parity(rng, torch.float32, 300, "small")
+
+
+def check_spmm_values_parity(rng, dtype, h, graph):
     n, m, rowptr, col = GRAPHS[graph](rng)
     rp, cc = dev_csr(rowptr, col)
     nnz = len(col)

@@ -97,6 +97,15 @@ def strides_of(graph, h, dtype):
 @pytest.mark.parametrize("h", [1, 9, 32, 100, 256])
 @pytest.mark.parametrize("graph", ["small", "hub"])
 def test_max_min_with_ties_are_bit_equal_to_the_shim(rng, dtype, h, graph):
+    check_max_min_with_ties(rng, dtype, h, graph)
+
+
+def test_max_min_over_three_feature_chunks(rng):
+    """h = 300: the misaligned stride gives 300 one-element pieces, three blockIdx.y chunks of 128, the last one partly empty"""
+    check_max_min_with_ties(rng, torch.float32, 300, "small")
+
+
+def check_max_min_with_ties(rng, dtype, h, graph):
     n, m, rowptr, col = GRAPHS[graph](rng)
     rp, cc = dev_csr(rowptr, col)
     nnz = len(col)
@@ -139,6 +148,36 @@ def test_max_min_on_continuous_inputs_are_bit_equal_to_the_shim(rng, dtype, h, g
 @pytest.mark.parametrize("h", [1, 9, 32, 100, 256])
 @pytest.mark.parametrize("graph", ["small", "hub"])
 def test_mean_parity(rng, dtype, h, graph):
+    check_mean_parity(rng, dtype, h, graph)
+
+
+def test_mean_parity_over_three_feature_chunks(rng):
+    check_mean_parity(rng, torch.float32, 300, "small")
+
+
+@pytest.mark.parametrize("dtype", FLOATS)
+@pytest.mark.parametrize("h", [9, 256])
+@pytest.mark.parametrize("graph", ["small", "hub"])
+def test_mean_is_the_sum_of_spmm_values_divided_by_the_count(rng, dtype, h, graph):
+    """the documented contract, bit for bit: the same walk and the same order as pygim_spmm_values with one head, then one IEEE
+    division by the row's number of stored entries (done here on the CPU); empty rows are 0"""
+    n, m, rowptr, col = GRAPHS[graph](rng)
+    rp, cc = dev_csr(rowptr, col)
+    nnz = len(col)
+    code = pim_ops.DTYPE_CODE[dtype]
+    X = torch.from_numpy(rng.uniform(-1, 1, size=(m, h))).to(DEV, dtype)
+    val = torch.from_numpy(rng.uniform(-2, 2, size=nnz)).to(DEV, dtype)
+    mean, _ = call_reduce(dtype, OP["mean"], n, rp, cc, val, X, h, False)
+    ws = torch.empty(max(_lib.spmm_values_workspace(code, n, nnz, h, 1), 16), dtype=torch.uint8, device=DEV)
+    total = torch.full((n, h), float("nan"), dtype=dtype, device=DEV)
+    _lib.spmm_values(code, n, rp.data_ptr(), cc.data_ptr(), nnz, val.data_ptr(), 1, X.data_ptr(), h, h, total.data_ptr(), h, ws.data_ptr(), ws.numel(),
+                     torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    count = torch.from_numpy(np.diff(rowptr)).clamp(min=1).to(dtype).unsqueeze(1)
+    assert torch.equal(mean.cpu(), total.cpu() / count)
+
+
+def check_mean_parity(rng, dtype, h, graph):
     n, m, rowptr, col = GRAPHS[graph](rng)
     rp, cc = dev_csr(rowptr, col)
     nnz = len(col)
