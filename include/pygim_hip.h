@@ -225,7 +225,7 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
  *   pygim_edge_softmax:  out[e, k] = exp(s[e, k] - m) / sum_{e' in row(e)} exp(s[e', k] - m), m the row's and head's maximum;
  *     scores and out: [nnz, heads] contiguous; the sum runs over the row's stored entries (duplicates are separate entries); stable
  *     for finite scores of any magnitude.
- *   pygim_edge_softmax_backward:  out[e, k] = P[e, k] * (dP[e, k] - sum_{e' in row(e)} P[e', k] * dP[e', k]).                */
+ *   pygim_edge_softmax_backward:  out[e, k] = P[e, k] * (dP[e, k] - sum_{e' in row(e)} P[e', k] * dP[e', k]).                          */
 int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
 int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values,
                       int64_t heads, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *workspace,
@@ -235,6 +235,24 @@ int pygim_edge_softmax(int dtype, int64_t nrows, const int32_t *rowptr, int64_t 
                        void *workspace, int64_t workspace_bytes, void *stream);
 int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr, int64_t nnz, const void *P, const void *dP,
                                 int64_t heads, void *out, void *workspace, int64_t workspace_bytes, void *stream);
+/*   pygim_gat_aggregate:  the aggregation of a GAT layer in one pass over the stored entries -- scores, softmax and product, with
+ *     nothing of size nnz read (besides colind) or written:
+ *       s[e, k]   = leaky_relu(a_dst[r, k] + a_src[colind[e], k], negative_slope)     e over the entries of row r, k = f / (h / heads)
+ *       out[r, f] = sum_e exp(s[e, k] - m[r, k]) * X[colind[e], f] / l[r, k],   m = max_e s,  l = sum_e exp(s - m)
+ *       lse[r, k] = m[r, k] + log(l[r, k])        when lse is not NULL ([nrows, heads] contiguous)
+ *     The contract of pygim_spmm_values: FLT32 and DBL64 only, device pointers only, a valid CSR guaranteed by the caller, nnz = 0,
+ *     empty rows and any h >= 1 allowed, heads >= 1 divides h, row strides ldx, ldo >= h, work is only enqueued on `stream`, scratch
+ *     from the caller (pygim_gat_aggregate_workspace bytes: a function of its arguments alone, -1 for bad arguments; 16-byte
+ *     aligned), no atomics, the same bits on every launch.  a_dst: [nrows, heads], a_src: [max column + 1, heads], both contiguous.
+ *     Duplicates are separate entries; empty rows store out = 0 and lse = 0; out has the same bits with and without lse.  An online
+ *     softmax (running maximum, rescaled sum and accumulator): stable for finite scores of any magnitude.  Within 2e-5 (FLT32) /
+ *     2e-12 (DBL64) of sum_e p[e] * |x[e]| of the exact value, p the exact probabilities: the bounds of pygim_edge_softmax and
+ *     pygim_spmm_values added.  PYGIM_ERR_INVALID: an integer type, heads not dividing h, a workspace too small or misaligned.    */
+int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
+int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                        const void *a_dst /* [nrows, heads] */, const void *a_src /* [ncols, heads] */, int64_t heads,
+                        double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo,
+                        void *lse /* [nrows, heads] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
  *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1

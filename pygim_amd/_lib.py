@@ -22,6 +22,7 @@ EXPORTS = [
     "pygim_group_lds_tiles", "pygim_group_lds_runs", "pygim_group_serial", "pygim_group_host_windows",
     "pygim_group_create_transposed", "pygim_sddmm",
     "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
+    "pygim_gat_aggregate", "pygim_gat_aggregate_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward",
 ]
 
@@ -71,6 +72,9 @@ def lib():
         L.pygim_edge_softmax_backward.argtypes = [c_int, c_i64, vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_edge_softmax_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
         L.pygim_edge_softmax_workspace.restype = c_i64
+        L.pygim_gat_aggregate.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, ctypes.c_double, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_gat_aggregate_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
+        L.pygim_gat_aggregate_workspace.restype = c_i64
         L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
@@ -224,6 +228,23 @@ def edge_softmax_backward(dtype, nrows, rowptr_ptr, nnz, p_ptr, dp_ptr, heads, o
     """out = P * (dP - sum_row P * dP): the gradient of edge_softmax with respect to the scores"""
     check(lib().pygim_edge_softmax_backward(int(dtype), int(nrows), _vp(rowptr_ptr), int(nnz), _vp(p_ptr), _vp(dp_ptr), int(heads),
                                             _vp(out_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def gat_aggregate_workspace(dtype, nrows, nnz, h, heads):
+    """bytes of scratch gat_aggregate needs for this shape (a function of the numbers alone)"""
+    n = int(lib().pygim_gat_aggregate_workspace(int(dtype), int(nrows), int(nnz), int(h), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad gat_aggregate_workspace arguments")
+    return n
+
+
+def gat_aggregate(dtype, nrows, rowptr_ptr, col_ptr, nnz, a_dst_ptr, a_src_ptr, heads, negative_slope, x_ptr, ldx, h, out_ptr, ldo, lse_ptr, ws_ptr,
+                  ws_bytes, stream=0):
+    """out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k])) * X[col[e], f] over the entries of row r, k the head of f, in
+    one pass; lse_ptr (0: not wanted) receives max + log(sum exp) per row and head (device pointers; FLT32 / DBL64)"""
+    check(lib().pygim_gat_aggregate(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(a_dst_ptr), _vp(a_src_ptr), int(heads),
+                                    float(negative_slope), _vp(x_ptr), int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr),
+                                    int(ws_bytes), _vp(stream)))
 
 
 def spmm_reduce_workspace(dtype, op, nrows, nnz, h):

@@ -1,4 +1,5 @@
-"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax`` and the structure they share.
+"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate`` and the
+structure they share.
 
 A device group (``to_pim_group``) freezes its edge values when it is created -- on the fast path they are compiled into the code
 stream -- so ``mul`` multiplies by those values for as long as the group lives.  Values that change between calls (attention
@@ -11,6 +12,10 @@ pygim_edge_softmax_backward: no atomics, the same bits on every run), differenti
 * :func:`spmm_values` ``out[r] = sum_e value[e, head] * X[col[e]]``; backward ``dX`` = the same kernel on the transposed structure,
   ``dvalue`` = one ``pygim_sddmm`` per head on strided views of ``G`` and ``X``.
 * :func:`edge_softmax` the softmax of per-entry scores over the stored entries of every row, per head.
+* :func:`gat_aggregate` the aggregation of a GAT layer in one pass (pygim_gat_aggregate): the score of an entry is
+  ``leaky_relu(a_dst[row] + a_src[col])``, a function of two per-node numbers, so scores, an online softmax and the product with ``X``
+  run inside the gather of ``spmm_values``.  Nothing of size nnz is written by the forward or kept for the backward (it saves
+  ``a_dst``, ``a_src``, ``X``, ``out`` and the per-row ``lse``); the backward recomputes the probabilities from them.
 
 Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph.
 """
@@ -220,3 +225,99 @@ def edge_softmax(graph, scores: torch.Tensor) -> torch.Tensor:
     home = scores.device
     P = EdgeSoftmax.apply(g, scores.to(g.device).reshape(g.nnz, heads).contiguous(), heads)
     return P.reshape(scores.shape).to(home)
+
+
+def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool):
+    """a_dst [nrows, heads], a_src [ncols, heads], X [ncols, h] contiguous on g.device -> (out [nrows, h], lse [nrows, heads] or None)"""
+    L, code = _backend()
+    h = X.size(1)
+    out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
+    lse = torch.empty((g.nrows, heads), dtype=X.dtype, device=g.device) if want_lse else None
+    if g.nrows == 0:
+        return out, lse
+    ws = _workspace(L.gat_aggregate_workspace(code[X.dtype], g.nrows, g.nnz, h, heads), g.device)
+    L.gat_aggregate(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
+                    X.data_ptr(), X.stride(0), h, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out, lse
+
+
+class GatAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, a_dst, a_src, X, slope):
+        heads = a_src.size(1)
+        need = any(ctx.needs_input_grad[1:4])
+        out, lse = _run_gat_aggregate(g, a_dst, a_src, X, heads, slope, need)
+        if need:
+            ctx.g, ctx.heads, ctx.slope = g, heads, slope
+            ctx.save_for_backward(a_dst, a_src, X, out, lse)   # node-sized, all of them
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        g, heads, slope = ctx.g, ctx.heads, ctx.slope
+        a_dst, a_src, X, out, lse = ctx.saved_tensors
+        G = G.contiguous()
+        h = X.size(1)
+        hd = h // heads
+        row, col = g.row.long(), g.col.long()
+        gt, perm = g.transposed()
+        # the probabilities again, from the node terms and the row's log-sum-exp: [nnz, heads], transient; in place where a tensor is done
+        # with.  The peak is at dp.t().contiguous(): p, dp, ds and the byte mask neg, beside the int64 row / col / perm indices
+        p = a_dst.index_select(0, row).add_(a_src.index_select(0, col))
+        neg = p < 0
+        torch.nn.functional.leaky_relu_(p, slope)
+        p.sub_(lse.index_select(0, row)).exp_()
+        dX = _run_spmm_values(gt, p.index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
+        da_dst = da_src = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            L, code = _backend()
+            es = X.element_size()
+            dp = torch.empty((heads, g.nnz), dtype=X.dtype, device=g.device)
+            if g.nnz > 0:
+                for k in range(heads):   # G[:, k * hd:(k + 1) * hd] . X[:, k * hd:(k + 1) * hd] per entry, as SpmmValues.backward does
+                    L.sddmm(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
+                            X.data_ptr() + k * hd * es, X.stride(0), hd, dp[k].data_ptr(), _stream(g.device))
+            ds = dp.t().contiguous()
+            del dp
+            delta = (G * out).view(g.nrows, heads, hd).sum(-1)   # = sum_e p * dp per (row, head), without a pass over the entries
+            ds.sub_(delta.index_select(0, row)).mul_(p)
+            del p
+            one = torch.ones((), dtype=X.dtype, device=g.device)
+            ds.mul_(torch.where(neg, one * slope, one))   # ds = p * (dp - delta[row]) * leaky_relu'(z)
+            del neg
+            if ctx.needs_input_grad[1]:   # row sums per head
+                da_dst = _run_spmm_values(g, ds, torch.ones((g.ncols, heads), dtype=X.dtype, device=g.device), heads)
+            if ctx.needs_input_grad[2]:   # column sums per head
+                da_src = _run_spmm_values(gt, ds.index_select(0, perm), torch.ones((g.nrows, heads), dtype=X.dtype, device=g.device), heads)
+        return None, da_dst, da_src, dX, None
+
+
+def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tensor, negative_slope: float = 0.2) -> torch.Tensor:
+    """the aggregation of a GAT layer, fused: with ``k = f // (h // heads)`` and e over the stored entries of row r
+
+    ``out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k], negative_slope)) * X[col[e], f]``
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; a_dst [rows, heads] and a_src [columns, heads] (1-D: one head);
+    X [columns, h] with ``h % heads == 0``; all three float32 or all float64.  Empty rows give 0; duplicates are separate entries.
+    One kernel, one pass over the entries; what ``edge_softmax`` + ``spmm_values`` on the composed scores give, without the
+    ``[nnz, heads]`` score and probability tensors.  Differentiable in ``a_dst``, ``a_src`` and ``X``: the forward saves only
+    node-sized tensors, the backward recomputes the probabilities and runs on ``spmm_values`` and ``pygim_sddmm`` (deterministic; its
+    ``[nnz, heads]`` tensors are transient, a fused backward kernel is not part of this).  Runs on the device; CPU tensors are staged
+    there and the result comes back to X's device.  No double backward."""
+    g = EdgeGraph.of(graph)
+    if X.dtype not in FLOAT_TYPES or a_dst.dtype != X.dtype or a_src.dtype != X.dtype:
+        raise TypeError(f"gat_aggregate: a_dst, a_src and X must all be float32 or float64, got {a_dst.dtype}, {a_src.dtype} and {X.dtype}")
+    if a_src.dim() == 1 and a_dst.dim() == 1:
+        a_src, a_dst = a_src.unsqueeze(1), a_dst.unsqueeze(1)
+    if a_src.dim() != 2 or a_dst.dim() != 2 or a_src.size(1) < 1 or a_dst.size(1) != a_src.size(1):
+        raise ValueError(f"gat_aggregate: a_dst and a_src must both be 1-D or both [nodes, heads], got {tuple(a_dst.shape)} and {tuple(a_src.shape)}")
+    heads = a_src.size(1)
+    if a_dst.size(0) != g.nrows or a_src.size(0) != g.ncols:
+        raise ValueError(f"gat_aggregate: a_dst must be [{g.nrows}, {heads}] and a_src [{g.ncols}, {heads}], got {tuple(a_dst.shape)} and {tuple(a_src.shape)}")
+    if X.dim() != 2 or X.size(0) != g.ncols:
+        raise ValueError(f"gat_aggregate: X must be [{g.ncols}, h], got {tuple(X.shape)}")
+    if X.size(1) < 1 or X.size(1) % heads != 0:
+        raise ValueError(f"gat_aggregate: heads = {heads} must divide h = {X.size(1)}")
+    home = X.device
+    out = GatAggregate.apply(g, a_dst.to(g.device).contiguous(), a_src.to(g.device).contiguous(), X.to(g.device).contiguous(), float(negative_slope))
+    return out.to(home)

@@ -25,6 +25,7 @@
 #include "sddmm_dev.hpp"
 #include "row_gather_dev.hpp"
 #include "edge_softmax_dev.hpp"
+#include "gat_aggregate_dev.hpp"
 #include "spmm_reduce_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -593,7 +594,7 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
 
 }  // extern "C"
 
-// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, spmm_reduce and its backward ----
+// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward ----
 // f(T()) with T the element type of `dtype` (the caller has checked it); INTS = false: FLT32 / DBL64 only
 template <bool INTS = false, typename F> static void with_elem_type(int dtype, F &&f) {
     if constexpr (INTS) {
@@ -679,6 +680,32 @@ int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int
         launch_row_gather<T, FoldSum<false>>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values,
                                              (uint32_t)heads, (const T *)X, (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, nullptr, workspace,
                                              (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
+    (void)nrows;
+    if (!is_float_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0) return -1;
+    return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, dtype_size(dtype));
+}
+
+int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
+                        int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32 or DBL64");
+    if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: heads must divide h");
+    if (int rc = check_csr_call("gat_aggregate", "rowptr / colind / a_dst / a_src / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {a_dst, nnz > 0}, {a_src, nnz > 0}, {X, nnz > 0}},
+                                pygim_gat_aggregate_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
+        return rc;
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_gat_aggregate<T>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
+                                (uint32_t)heads, (T)negative_slope, (const T *)X, (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, (T *)lse, workspace,
+                                (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;

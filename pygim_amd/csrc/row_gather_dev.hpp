@@ -21,6 +21,9 @@
 // No atomics; every fold has a fixed order (entry order inside a run, the xor tree, then the runs in order): the same bits on every
 // launch.
 //
+// k_gat_gather / k_gat_fixup / k_gat_empty (gat_aggregate_dev.hpp) are a copy of this walker -- batch loop, row search, flush, slot
+// addressing, fix-up -- with an online softmax in place of the Fold: a change to the walk here has to be made there as well.
+//
 // A Fold says what the walker cannot know:
 //   INDEXED   the partial result is a pair (value, index of the entry that holds it): aidx, the index slots and arg exist
 //   PER_HEAD  values holds `heads` weights per entry and feature f takes weight f / (h / heads); else one weight per entry, 1 without values

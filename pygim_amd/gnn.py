@@ -14,6 +14,8 @@ x and the result are then this rank's row block).
 
 GATConv / GAT are the attention layer on top of pygim_amd.attention: its edge weights are computed on every call, so its aggregation
 is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values frozen in the group); float32 / float64, trainable.
+``GATConv(..., fused=True)`` / ``GAT(..., fused=True)`` aggregate with ``gat_aggregate`` instead: scores, softmax and product in one
+kernel, no ``[nnz, heads]`` tensor written or kept for the backward.  The default (``fused=False``) is the layer as before.
 """
 import torch
 import torch.nn.functional as F
@@ -68,10 +70,12 @@ class GINConv(torch.nn.Module):
 class GATConv(torch.nn.Module):
     """PyG's GATConv arithmetic on the adjacency as given (no self loops are inserted, like the other layers here):
     x' = lin(x) as [N, H, F];  score of stored entry (i, j) = leaky_relu(a_dst[i] + a_src[j]) with a = (x' * att).sum(-1);
-    p = softmax of the scores over the entries of row i;  out[i] = sum_j p[(i, j)] * x'[j] per head; heads concatenated or averaged."""
+    p = softmax of the scores over the entries of row i;  out[i] = sum_j p[(i, j)] * x'[j] per head; heads concatenated or averaged.
+    ``fused=True``: everything after the two reductions ``a`` is one ``gat_aggregate`` call."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, **_):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused=False, **_):
         super().__init__()
+        self.fused = bool(fused)
         self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
         self.lin = Linear(in_channels, self.heads * self.out_channels, bias=False)
         self.att_src = torch.nn.Parameter(torch.empty(1, self.heads, self.out_channels))
@@ -82,17 +86,20 @@ class GATConv(torch.nn.Module):
         torch.nn.init.xavier_uniform_(self.att_dst)
 
     def forward(self, x, adj_t):
-        from .attention import EdgeGraph, edge_softmax, spmm_values
+        from .attention import EdgeGraph, edge_softmax, gat_aggregate, spmm_values
 
         g = EdgeGraph.of(adj_t)
         H, F_ = self.heads, self.out_channels
         xp = self.lin(x).view(-1, H, F_)
         a_src = (xp * self.att_src).sum(-1)
         a_dst = (xp * self.att_dst).sum(-1)
-        row, col = g.row.long().to(x.device), g.col.long().to(x.device)
-        score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
-        p = edge_softmax(g, score)
-        out = spmm_values(g, p, xp.reshape(-1, H * F_), heads=H)
+        if self.fused:
+            out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope)
+        else:
+            row, col = g.row.long().to(x.device), g.col.long().to(x.device)
+            score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
+            p = edge_softmax(g, score)
+            out = spmm_values(g, p, xp.reshape(-1, H * F_), heads=H)
         if not self.concat:
             out = out.view(-1, H, F_).mean(1)
         return out if self.bias is None else out + self.bias
@@ -149,7 +156,7 @@ class GIN(_Stack):
 
 
 class GAT(_Stack):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=False):
         assert hidden_channels % heads == 0, "GAT: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
-                         lambda h: GATConv(h, h // heads, heads=heads, concat=True))
+                         lambda h: GATConv(h, h // heads, heads=heads, concat=True, fused=fused))

@@ -6,8 +6,14 @@ warm-up.  JSON lines:
     (c) the frozen-values product mul: the code stream, and the sweep (lds_mode = 2);
   edge_softmax forward and backward at heads = 8 (time, bytes moved / time) next to the torch composite (index_reduce_ amax, exp,
     index_add_, divide);
-  the bytes both *_workspace functions return for this shape.
-    python scripts/exp_attention.py [--iters 10]"""
+  the bytes both *_workspace functions return for this shape;
+  the fused GAT aggregation, after everything above (heads = 8, the same graph, two rounds in the same run):
+    (a) gat_aggregate forward; (b) the unfused sequence of GATConv for the same inputs -- score composite + edge_softmax +
+    spmm_values -- and each part on its own; (c) spmm_values heads = 8 alone, the floor of the gather; (d) forward + backward of
+    both paths with torch.cuda.max_memory_allocated for each.
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused] [--forward-only]
+  --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
+  (profiles/exp_gat_fused.txt)."""
 import argparse
 import json
 import os
@@ -35,25 +41,81 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--h", type=int, default=256)
-    ap.add_argument("--shape", default="reddit")
-    args = ap.parse_args()
-    dev = torch.device("cuda", 0)
-    n, nnz, d_max = synth.SHAPES[args.shape]
-    h, iters = args.h, args.iters
-    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
-    pim_ops.load("spmm")
-    torch.ops.pim_ops.dpu_init_ranks(1)
-    g = attention.EdgeGraph(rowptr, col, (n, n))
-    x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform")
+def fused_section(g, x, n, nnz, h, iters, dev, line, backward=True):
+    """the fused GAT aggregation next to the three passes it replaces, heads = 8"""
+    import torch.nn.functional as F
+
+    heads, slope = 8, 0.2
+    gen = torch.Generator(device=dev).manual_seed(2)
+    a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+    a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+    row, col = g.row.long(), g.col.long()
+
+    def score():
+        return F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), slope)
+
+    def unfused():
+        return attention._run_spmm_values(g, attention._run_edge_softmax(g, score(), None, heads), x, heads)
+
+    s = score()
+    P = attention._run_edge_softmax(g, s, None, heads)
+    got = attention._run_gat_aggregate(g, a_dst, a_src, x, heads, slope, False)[0]
+    agree = bool(torch.allclose(got, attention._run_spmm_values(g, P, x, heads), rtol=1e-4, atol=1e-5))
+    del got
+    for rnd in range(2):
+        ta = timed(lambda: attention._run_gat_aggregate(g, a_dst, a_src, x, heads, slope, False), iters)
+        tl = timed(lambda: attention._run_gat_aggregate(g, a_dst, a_src, x, heads, slope, True), iters)
+        tb = timed(unfused, iters)
+        ts = timed(score, iters)
+        te = timed(lambda: attention._run_edge_softmax(g, s, None, heads), iters)
+        tc = timed(lambda: attention._run_spmm_values(g, P, x, heads), iters)
+        line(what="gat fused vs unfused forward, heads=8", round=rnd, a_gat_aggregate_ms=round(ta, 3), a_with_lse_ms=round(tl, 3), b_unfused_ms=round(tb, 3),
+             b_score_composite_ms=round(ts, 3), b_edge_softmax_ms=round(te, 3), c_spmm_values_heads8_ms=round(tc, 3), a_over_b=round(ta / tb, 4),
+             a_over_c=round(ta / tc, 4), gather_tb_s=round(nnz * h * 4 / ta / 1e9, 2), same_result=agree)
+    del s, P
+    line(what="gat workspace bytes", gat_aggregate=_lib.gat_aggregate_workspace(_lib.FLT32, n, nnz, h, heads),
+         spmm_values=_lib.spmm_values_workspace(_lib.FLT32, n, nnz, h, heads))
+
+    if not backward:
+        return
+
+    # ---- (d) forward + backward of both paths, peak memory of each ----
+    G = synth.features(n, h, torch.float32, seed=2, device=dev, kind="uniform")
+    leaves = [t.clone().requires_grad_() for t in (a_dst, a_src, x)]
+    g.transposed()   # built once per graph, before either path is measured
+
+    def fused_step():
+        for t in leaves:
+            t.grad = None
+        attention.gat_aggregate(g, *leaves, slope).backward(G)
+
+    def unfused_step():   # gnn.GATConv.forward between the two reductions and the concat
+        for t in leaves:
+            t.grad = None
+        r, c = g.row.long(), g.col.long()
+        sc = F.leaky_relu(leaves[0].index_select(0, r) + leaves[1].index_select(0, c), slope)
+        attention.spmm_values(g, attention.edge_softmax(g, sc), leaves[2], heads=heads).backward(G)
+
+    del row, col
+    res = {}
+    for name, step in (("fused", fused_step), ("unfused", unfused_step)):
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ms = timed(step, max(2, iters // 3))
+        res[name] = (ms, base, torch.cuda.max_memory_allocated())
+    line(what="gat forward + backward, heads=8", fused_ms=round(res["fused"][0], 2), unfused_ms=round(res["unfused"][0], 2),
+         fused_peak_bytes=res["fused"][2], unfused_peak_bytes=res["unfused"][2], allocated_before_bytes=res["fused"][1],
+         fused_peak_above_start_gb=round((res["fused"][2] - res["fused"][1]) / 1e9, 2),
+         unfused_peak_above_start_gb=round((res["unfused"][2] - res["unfused"][1]) / 1e9, 2), nnz_heads_tensor_gb=round(nnz * heads * 4 / 1e9, 2))
+
+
+def base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line):
+    """spmm_values, edge_softmax, the workspaces, new values through a new group: the record in profiles/exp_attention.txt"""
     gen = torch.Generator(device=dev).manual_seed(1)
     gathered = nnz * h * 4
-
-    def line(**kw):
-        print(json.dumps({"graph": args.shape, "h": h, "nnz": nnz, **kw}), flush=True)
 
     # ---- spmm_values, alternating with pygim_sddmm (two rounds: the spread) ----
     v1 = torch.rand(nnz, 1, device=dev, generator=gen)
@@ -129,6 +191,32 @@ def main():
     _lib.set_tunable("lds_mode", old)
     line(what="new values per step", regroup_then_mul_ms=round(regroup_ms, 2), spmm_values_heads1_ms=round(t1, 3), ratio=round(regroup_ms / t1, 2),
          same_product=agree, frozen_mul_ms=round(mul_code, 3), frozen_mul_form=note[:120], frozen_mul_sweep_ms=round(mul_sweep, 3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--h", type=int, default=256)
+    ap.add_argument("--shape", default="reddit")
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused"])
+    ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    n, nnz, d_max = synth.SHAPES[args.shape]
+    h, iters = args.h, args.iters
+    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    g = attention.EdgeGraph(rowptr, col, (n, n))
+    x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform")
+
+    def line(**kw):
+        print(json.dumps({"graph": args.shape, "h": h, "nnz": nnz, **kw}), flush=True)
+
+    if args.section in ("all", "base"):
+        base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line)
+    if args.section in ("all", "fused"):   # after the recorded parts, which keep the allocator and cache state they were taken under
+        fused_section(g, x, n, nnz, h, iters, dev, line, backward=not args.forward_only)
     torch.ops.pim_ops.dpu_release()
 
 
