@@ -59,8 +59,32 @@ typedef enum {
     PYGIM_INT32 = 2,
     PYGIM_INT64 = 3,
     PYGIM_FLT32 = 4,
-    PYGIM_DBL64 = 5
+    PYGIM_DBL64 = 5,
+    /* 16-bit FEATURE types (IEEE binary16, bfloat16).  Valid only for pygim_sddmm, pygim_spmm_values, pygim_gat_aggregate,
+     * pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
+     * point -- group creation, edge softmax, the max / min reductions and their backward, the quantisers -- rejects them like
+     * an unknown type. */
+    PYGIM_FLT16 = 6,
+    PYGIM_BF16 = 7
 } pygim_dtype;
+
+/* ---- 16-bit features ----
+ * With PYGIM_FLT16 / PYGIM_BF16 the feature matrices are STORED in 16 bits and everything else is float32:
+ *   pygim_sddmm          G, X 16-bit;      out [nnz] float32 (nothing is rounded)
+ *   pygim_spmm_values    X, out 16-bit;    values float32
+ *   pygim_gat_aggregate  X, out 16-bit;    a_dst, a_src, lse float32
+ *   pygim_spmm_reduce    X, out 16-bit;    values float32 or NULL; PYGIM_REDUCE_MEAN only (MAX / MIN: PYGIM_ERR_INVALID)
+ * Strides (ldx, ldo, ldg) count 16-bit elements.  An element of X is widened to float32 as it is read (exact) and the arithmetic is
+ * the FLT32 arithmetic of the call: accumulators, the exchange between lane groups, the workspace slots of rows cut across waves and
+ * the kernels that join them, the online-softmax state (m, l, acc), the mean's division and lse are float32 -- so the *_workspace
+ * functions return the FLT32 sizes for these codes.  A result is rounded ONCE, round-to-nearest-even, where a finished row is
+ * stored into out (NaN stays NaN; a FLT16 result beyond 65504 becomes +-inf).  Empty rows store 16-bit zeros (lse = 0.0f).
+ * Bounds, with u = 2^-11 (FLT16) / 2^-8 (BF16), the half-ulp of that one rounding, and `exact` the exact result on the 16-bit inputs:
+ *   spmm_values, mean     |out - exact| <= u |exact| + the FLT32 bound of the call (1e-5 sum |value . x|; the mean's divided by the count)
+ *   gat_aggregate         |out - exact| <= u |exact| + 2e-5 sum_e p[e] |x[e]|;  lse as for FLT32
+ *   sddmm                 the FLT32 bound (1e-5 sum_f |G . X|)
+ * 16-byte gathers need (h / heads) % 8 == 0, strides that are multiples of 8 elements and 16-byte aligned X / G / out; otherwise a
+ * lane reads one element.  No atomics and fixed orders as for FLT32: the same bits on every launch. */
 
 typedef enum { PYGIM_CSR = 0, PYGIM_COO = 1 } pygim_format;
 
@@ -203,7 +227,8 @@ int pygim_spmm_run_dequant(int64_t handle, const void *Xq, int64_t ldx, float *o
 /* ---- sampled dense-dense product (the gradient of an aggregation with respect to the edge values) ----
  *   out[e] = sum_f G[row(e), f] * X[colind[e], f]   for every stored entry e of the CSR (rowptr: nrows + 1, colind: nnz),
  * in stored order.  G: [nrows, h] with row stride ldg, X: [max column + 1, h] with row stride ldx, out: nnz elements; any
- * h >= 1, nnz = 0 and empty rows allowed.  FLT32 and DBL64 only (else PYGIM_ERR_INVALID); device pointers only, the
+ * h >= 1, nnz = 0 and empty rows allowed.  FLT32 and DBL64 (FLT16 / BF16: G and X 16-bit, out float32 -- "16-bit features" above), else
+ * PYGIM_ERR_INVALID; device pointers only, the
  * caller guarantees a valid CSR (rowptr non-decreasing from 0 to nnz, column ids inside X).  Every entry owns its output:
  * no atomics, the same bits on every run; each sum is a fixed-order sum over the features (within 1e-5 (FLT32) /
  * 1e-12 (DBL64) of sum_f |G . X| of the exact value).  Only enqueues work on `stream`.                                */
@@ -212,7 +237,7 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
 
 /* ---- products and softmax whose edge values are an operand of the call (attention, gates, learned normalisation) ----
  * Functional entry points on a caller's CSR like pygim_sddmm: no group handle, device pointers only, FLT32 and DBL64 only (else
- * PYGIM_ERR_INVALID), int32 rowptr / colind with nnz <= 2^31 - 1, a valid CSR guaranteed by the caller.  nnz = 0, empty rows and any
+ * PYGIM_ERR_INVALID; pygim_spmm_values also takes FLT16 / BF16 with float32 values -- "16-bit features" above), int32 rowptr / colind with nnz <= 2^31 - 1, a valid CSR guaranteed by the caller.  nnz = 0, empty rows and any
  * h >= 1 are allowed.  They only enqueue work on `stream`: no allocation, no synchronisation.  Scratch comes from the caller:
  * `workspace` holds at least the bytes the matching *_workspace function returns (a function of its arguments alone, never of the
  * CSR's contents; -1 for bad arguments), is 16-byte aligned, and must not be shared by calls that may overlap.  No float atomics:
@@ -240,7 +265,7 @@ int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr,
  *       s[e, k]   = leaky_relu(a_dst[r, k] + a_src[colind[e], k], negative_slope)     e over the entries of row r, k = f / (h / heads)
  *       out[r, f] = sum_e exp(s[e, k] - m[r, k]) * X[colind[e], f] / l[r, k],   m = max_e s,  l = sum_e exp(s - m)
  *       lse[r, k] = m[r, k] + log(l[r, k])        when lse is not NULL ([nrows, heads] contiguous)
- *     The contract of pygim_spmm_values: FLT32 and DBL64 only, device pointers only, a valid CSR guaranteed by the caller, nnz = 0,
+ *     The contract of pygim_spmm_values: FLT32 and DBL64 (FLT16 / BF16: X and out 16-bit, a_dst / a_src / lse float32), device pointers only, a valid CSR guaranteed by the caller, nnz = 0,
  *     empty rows and any h >= 1 allowed, heads >= 1 divides h, row strides ldx, ldo >= h, work is only enqueued on `stream`, scratch
  *     from the caller (pygim_gat_aggregate_workspace bytes: a function of its arguments alone, -1 for bad arguments; 16-byte
  *     aligned), no atomics, the same bits on every launch.  a_dst: [nrows, heads], a_src: [max column + 1, heads], both contiguous.
@@ -260,7 +285,7 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
  *     empty rows and any h >= 1 allowed, row strides ldx, ldo >= h, work is only enqueued on `stream`, scratch from the caller
  *     (pygim_spmm_reduce_workspace bytes: a function of its arguments alone, -1 for bad arguments; 16-byte aligned), no atomics, the
  *     same bits on every launch.  Empty rows store 0.
- *     MEAN (FLT32 / DBL64): the sum of pygim_spmm_values, in its order and within its bound, divided by the row's number of stored
+ *     MEAN (FLT32 / DBL64; FLT16 / BF16 with float32 values -- "16-bit features" above): the sum of pygim_spmm_values, in its order and within its bound, divided by the row's number of stored
  *       entries (duplicates count separately; not the sum of the values).  arg must be NULL.
  *     MAX / MIN (all six types): integers compare as signed values of their type and the integer product wraps like the type's own
  *       arithmetic; a float result is exactly one of the products.  arg, when not NULL ([nrows, h] int32, contiguous), receives the
@@ -272,7 +297,8 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
  *     rowptr_t [ncols + 1], rows_t [nnz] (the A-row of every entry of A^T) and perm [nnz] (its index in A: the stable sort of A's
  *     entries by column) describe A^T; values are in A's order or NULL; arg is the forward's.  dX[0:ncols, 0:h] (row stride ldd) is
  *     overwritten; every output row has one owner.  Within 1e-5 (FLT32) / 1e-12 (DBL64) of sum |w . G| of the exact value.
- *   PYGIM_ERR_INVALID: an unknown op, an integer type with MEAN or with the backward, arg with MEAN, a workspace that is too small. */
+ *   PYGIM_ERR_INVALID: an unknown op, an integer type with MEAN or with the backward, a 16-bit type with MAX / MIN or with the backward,
+ *     arg with MEAN, a workspace that is too small. */
 #define PYGIM_REDUCE_MEAN 1
 #define PYGIM_REDUCE_MAX 2
 #define PYGIM_REDUCE_MIN 3

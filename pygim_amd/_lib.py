@@ -28,6 +28,7 @@ EXPORTS = [
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
 INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
+FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
 
@@ -186,7 +187,7 @@ def group_create_transposed(fmt, dtype, idx0_ptrs, col_ptrs, val_ptrs, nrows, nc
 
 
 def sddmm(dtype, nrows, rowptr_ptr, col_ptr, nnz, g_ptr, ldg, x_ptr, ldx, h, out_ptr, stream=0):
-    """out[e] = G[row(e)] . X[col[e]] for every stored entry of a CSR (device pointers; FLT32 / DBL64)"""
+    """out[e] = G[row(e)] . X[col[e]] for every stored entry of a CSR (device pointers; FLT32 / DBL64, or FLT16 / BF16 G and X with a float32 out)"""
     check(lib().pygim_sddmm(int(dtype), int(nrows), ctypes.c_void_p(rowptr_ptr or None), ctypes.c_void_p(col_ptr or None), int(nnz),
                             ctypes.c_void_p(g_ptr or None), int(ldg), ctypes.c_void_p(x_ptr or None), int(ldx), int(h),
                             ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
@@ -205,7 +206,8 @@ def spmm_values_workspace(dtype, nrows, nnz, h, heads):
 
 
 def spmm_values(dtype, nrows, rowptr_ptr, col_ptr, nnz, val_ptr, heads, x_ptr, ldx, h, out_ptr, ldo, ws_ptr, ws_bytes, stream=0):
-    """out[r, f] = sum_e values[e, head of f] * X[col[e], f] over the entries of row r (device pointers; FLT32 / DBL64)"""
+    """out[r, f] = sum_e values[e, head of f] * X[col[e], f] over the entries of row r (device pointers; FLT32 / DBL64, or FLT16 / BF16 X and out with
+    float32 values)"""
     check(lib().pygim_spmm_values(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(val_ptr), int(heads), _vp(x_ptr),
                                   int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
 
@@ -241,7 +243,8 @@ def gat_aggregate_workspace(dtype, nrows, nnz, h, heads):
 def gat_aggregate(dtype, nrows, rowptr_ptr, col_ptr, nnz, a_dst_ptr, a_src_ptr, heads, negative_slope, x_ptr, ldx, h, out_ptr, ldo, lse_ptr, ws_ptr,
                   ws_bytes, stream=0):
     """out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k])) * X[col[e], f] over the entries of row r, k the head of f, in
-    one pass; lse_ptr (0: not wanted) receives max + log(sum exp) per row and head (device pointers; FLT32 / DBL64)"""
+    one pass; lse_ptr (0: not wanted) receives max + log(sum exp) per row and head (device pointers; FLT32 / DBL64, or FLT16 / BF16 X and out
+    with float32 a_dst, a_src and lse)"""
     check(lib().pygim_gat_aggregate(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(a_dst_ptr), _vp(a_src_ptr), int(heads),
                                     float(negative_slope), _vp(x_ptr), int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr),
                                     int(ws_bytes), _vp(stream)))
@@ -257,7 +260,7 @@ def spmm_reduce_workspace(dtype, op, nrows, nnz, h):
 
 def spmm_reduce(dtype, op, nrows, rowptr_ptr, col_ptr, nnz, val_ptr, x_ptr, ldx, h, out_ptr, ldo, arg_ptr, ws_ptr, ws_bytes, stream=0):
     """out[r, f] = mean / max / min over the entries e of row r of values[e] * X[col[e], f] (REDUCE_*; val_ptr 0: unit weights;
-    arg_ptr: int32 [nrows, h] for the winning entry of max / min, or 0)"""
+    arg_ptr: int32 [nrows, h] for the winning entry of max / min, or 0; FLT16 / BF16 X and out with float32 values: REDUCE_MEAN only)"""
     check(lib().pygim_spmm_reduce(int(dtype), int(op), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(val_ptr), _vp(x_ptr), int(ldx),
                                   int(h), _vp(out_ptr), int(ldo), _vp(arg_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
 

@@ -17,13 +17,22 @@ pygim_edge_softmax_backward: no atomics, the same bits on every run), differenti
   run inside the gather of ``spmm_values``.  Nothing of size nnz is written by the forward or kept for the backward (it saves
   ``a_dst``, ``a_src``, ``X``, ``out`` and the per-row ``lse``); the backward recomputes the probabilities from them.
 
-Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph.
+16-bit features: ``X`` of ``spmm_values`` and ``gat_aggregate`` (and of ``spmm_reduce(..., "mean")``, ``autograd.sddmm``) may be
+bfloat16 or float16 -- what ``model.to(torch.bfloat16)`` and ``torch.autocast`` hand a layer.  Only the feature matrices are stored
+in 16 bits: edge values, ``a_dst`` / ``a_src``, ``lse``, every partial sum and the softmax state are float32 (the wrappers upcast
+16-bit values and node terms), and a result row is rounded once, to nearest even, where it is stored.  ``edge_softmax`` stays float32 /
+float64.
+
+Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph, 16-bit device groups
+(``mul``), 16-bit ``edge_softmax`` and 16-bit max / min.
 """
 from __future__ import annotations
 
 import torch
 
 FLOAT_TYPES = (torch.float32, torch.float64)
+HALF_TYPES = (torch.float16, torch.bfloat16)
+HALF_CODE = {torch.float16: 6, torch.bfloat16: 7}   # PYGIM_FLT16 / PYGIM_BF16: feature types of the gather family only, never a group's
 
 
 def _backend():
@@ -33,6 +42,18 @@ def _backend():
     if not L.is_initialized():
         L.init_ranks(1)
     return L, pim_ops.DTYPE_CODE
+
+
+def _gather_code(dtype) -> int:
+    """the pygim_dtype of a feature matrix of the gather family (sddmm, spmm_values, gat_aggregate, spmm_reduce mean)"""
+    if dtype in HALF_CODE:
+        return HALF_CODE[dtype]
+    return _backend()[1][dtype]
+
+
+def _compute_dtype(dtype):
+    """what values, node terms, partial sums and lse are held in beside features of ``dtype``: float32 for the 16-bit types"""
+    return torch.float32 if dtype in HALF_TYPES else dtype
 
 
 def _device_for(t: torch.Tensor) -> torch.device:
@@ -118,15 +139,16 @@ def _stream(dev) -> int:
 
 
 def _run_spmm_values(g: EdgeGraph, value: torch.Tensor, X: torch.Tensor, heads: int) -> torch.Tensor:
-    """value [nnz, heads] and X [ncols, h] contiguous on g.device -> [nrows, h]"""
-    L, code = _backend()
+    """value [nnz, heads] (float32 beside 16-bit X, else X's dtype) and X [ncols, h] contiguous on g.device -> [nrows, h] in X's dtype"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
     h = X.size(1)
     out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
     if g.nrows == 0:
         return out
-    nbytes = L.spmm_values_workspace(code[X.dtype], g.nrows, g.nnz, h, heads)
+    nbytes = L.spmm_values_workspace(dt, g.nrows, g.nnz, h, heads)
     ws = _workspace(nbytes, g.device)
-    L.spmm_values(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, value.data_ptr(), heads, X.data_ptr(), X.stride(0), h,
+    L.spmm_values(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, value.data_ptr(), heads, X.data_ptr(), X.stride(0), h,
                   out.data_ptr(), h, ws.data_ptr(), ws.numel(), _stream(g.device))
     return out
 
@@ -148,13 +170,13 @@ class SpmmValues(torch.autograd.Function):
             gt, perm = g.transposed()
             dX = _run_spmm_values(gt, value.index_select(0, perm), G, heads)
         if ctx.needs_input_grad[1]:
-            L, code = _backend()
+            L, _ = _backend()
             h = X.size(1)
             hd, es = h // heads, X.element_size()
-            per_head = torch.empty((heads, g.nnz), dtype=X.dtype, device=g.device)
+            per_head = torch.empty((heads, g.nnz), dtype=value.dtype, device=g.device)   # float32 beside 16-bit G and X
             if g.nnz > 0:
                 for k in range(heads):   # G[:, k * hd:(k + 1) * hd] . X[:, k * hd:(k + 1) * hd] per entry: strided views of both
-                    L.sddmm(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
+                    L.sddmm(_gather_code(X.dtype), g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
                             X.data_ptr() + k * hd * es, X.stride(0), hd, per_head[k].data_ptr(), _stream(g.device))
             dvalue = per_head.t().contiguous()
         return None, dvalue, dX, None
@@ -164,12 +186,17 @@ def spmm_values(graph, value: torch.Tensor, X: torch.Tensor, heads: int = 1) -> 
     """``out[r, f] = sum over the stored entries e of row r of value[e, f // (h // heads)] * X[col[e], f]``
 
     graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; value [nnz] (heads = 1) or [nnz, heads]; X [columns, h] with
-    ``h % heads == 0``; value and X both float32 or both float64.  Differentiable in value and X.  Runs on the device; CPU tensors are
-    staged there and the result comes back to X's device."""
+    ``h % heads == 0``; value and X both float32 or both float64.  X may also be bfloat16 / float16 with value float32 or X's dtype:
+    the values are then taken as float32, the sums are float32 and ``out`` (X's dtype) is rounded once per element.  Differentiable
+    in value and X, each gradient in its operand's dtype (``dX``: the same kernel on the transposed structure; ``dvalue``: a float32
+    ``pygim_sddmm``).  Runs on the device; CPU tensors are staged there and the result comes back to X's device."""
     g = EdgeGraph.of(graph)
     heads = int(heads)
-    if X.dtype not in FLOAT_TYPES or value.dtype != X.dtype:
-        raise TypeError(f"spmm_values: value and X must both be float32 or float64, got {value.dtype} and {X.dtype}")
+    if X.dtype in HALF_TYPES:
+        if value.dtype not in (torch.float32, X.dtype):
+            raise TypeError(f"spmm_values: beside {X.dtype} features value must be float32 or {X.dtype}, got {value.dtype}")
+    elif X.dtype not in FLOAT_TYPES or value.dtype != X.dtype:
+        raise TypeError(f"spmm_values: value and X must both be float32 or float64 (or X bfloat16 / float16), got {value.dtype} and {X.dtype}")
     if X.dim() != 2 or X.size(0) != g.ncols:
         raise ValueError(f"spmm_values: X must be [{g.ncols}, h], got {tuple(X.shape)}")
     if heads < 1 or X.size(1) < 1 or X.size(1) % heads != 0:
@@ -179,7 +206,7 @@ def spmm_values(graph, value: torch.Tensor, X: torch.Tensor, heads: int = 1) -> 
     if value.dim() != 2 or value.size(0) != g.nnz or value.size(1) != heads:
         raise ValueError(f"spmm_values: value must be [{g.nnz}] or [{g.nnz}, {heads}], got {tuple(value.shape)}")
     home = X.device
-    out = SpmmValues.apply(g, value.to(g.device).contiguous(), X.to(g.device).contiguous(), heads)
+    out = SpmmValues.apply(g, value.to(g.device, _compute_dtype(X.dtype)).contiguous(), X.to(g.device).contiguous(), heads)
     return out.to(home)
 
 
@@ -228,15 +255,17 @@ def edge_softmax(graph, scores: torch.Tensor) -> torch.Tensor:
 
 
 def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool):
-    """a_dst [nrows, heads], a_src [ncols, heads], X [ncols, h] contiguous on g.device -> (out [nrows, h], lse [nrows, heads] or None)"""
-    L, code = _backend()
+    """a_dst [nrows, heads], a_src [ncols, heads] (float32 beside 16-bit X, else X's dtype), X [ncols, h] contiguous on g.device ->
+    (out [nrows, h] in X's dtype, lse [nrows, heads] in a_dst's or None)"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
     h = X.size(1)
     out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
-    lse = torch.empty((g.nrows, heads), dtype=X.dtype, device=g.device) if want_lse else None
+    lse = torch.empty((g.nrows, heads), dtype=a_dst.dtype, device=g.device) if want_lse else None   # float32 beside 16-bit X
     if g.nrows == 0:
         return out, lse
-    ws = _workspace(L.gat_aggregate_workspace(code[X.dtype], g.nrows, g.nnz, h, heads), g.device)
-    L.gat_aggregate(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
+    ws = _workspace(L.gat_aggregate_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
+    L.gat_aggregate(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
                     X.data_ptr(), X.stride(0), h, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
     return out, lse
 
@@ -270,25 +299,33 @@ class GatAggregate(torch.autograd.Function):
         dX = _run_spmm_values(gt, p.index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
         da_dst = da_src = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            L, code = _backend()
+            L, _ = _backend()
             es = X.element_size()
-            dp = torch.empty((heads, g.nnz), dtype=X.dtype, device=g.device)
+            ct = a_dst.dtype   # float32 beside 16-bit G, X and out: p, dp, delta and ds are never held in 16 bits
+            dp = torch.empty((heads, g.nnz), dtype=ct, device=g.device)
             if g.nnz > 0:
                 for k in range(heads):   # G[:, k * hd:(k + 1) * hd] . X[:, k * hd:(k + 1) * hd] per entry, as SpmmValues.backward does
-                    L.sddmm(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
+                    L.sddmm(_gather_code(X.dtype), g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, G.data_ptr() + k * hd * es, h,
                             X.data_ptr() + k * hd * es, X.stride(0), hd, dp[k].data_ptr(), _stream(g.device))
             ds = dp.t().contiguous()
             del dp
-            delta = (G * out).view(g.nrows, heads, hd).sum(-1)   # = sum_e p * dp per (row, head), without a pass over the entries
+            if X.dtype in HALF_TYPES:
+                # out was rounded to 16 bits when it was stored: G . out would carry that rounding (2^-9 of sum |G . out|) into every
+                # gradient of a row.  sum_e p * dp itself, as a float32 row sum per head (the gather of da_dst below)
+                delta = _run_spmm_values(g, p * ds, torch.ones((g.ncols, heads), dtype=ct, device=g.device), heads)
+            else:
+                delta = (G * out).view(g.nrows, heads, hd).sum(-1)   # = sum_e p * dp per (row, head), without a pass over the entries
             ds.sub_(delta.index_select(0, row)).mul_(p)
             del p
-            one = torch.ones((), dtype=X.dtype, device=g.device)
+            one = torch.ones((), dtype=ct, device=g.device)
             ds.mul_(torch.where(neg, one * slope, one))   # ds = p * (dp - delta[row]) * leaky_relu'(z)
             del neg
+            # the two sums per head run on ones of the compute type (FLT32 beside 16-bit features: a 16-bit call would round a sum over
+            # a whole row to 8 or 11 bits)
             if ctx.needs_input_grad[1]:   # row sums per head
-                da_dst = _run_spmm_values(g, ds, torch.ones((g.ncols, heads), dtype=X.dtype, device=g.device), heads)
+                da_dst = _run_spmm_values(g, ds, torch.ones((g.ncols, heads), dtype=ct, device=g.device), heads)
             if ctx.needs_input_grad[2]:   # column sums per head
-                da_src = _run_spmm_values(gt, ds.index_select(0, perm), torch.ones((g.nrows, heads), dtype=X.dtype, device=g.device), heads)
+                da_src = _run_spmm_values(gt, ds.index_select(0, perm), torch.ones((g.nrows, heads), dtype=ct, device=g.device), heads)
         return None, da_dst, da_src, dX, None
 
 
@@ -298,15 +335,22 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
     ``out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k], negative_slope)) * X[col[e], f]``
 
     graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; a_dst [rows, heads] and a_src [columns, heads] (1-D: one head);
-    X [columns, h] with ``h % heads == 0``; all three float32 or all float64.  Empty rows give 0; duplicates are separate entries.
+    X [columns, h] with ``h % heads == 0``; all three float32 or all float64.  X may also be bfloat16 / float16, with a_dst and a_src
+    both float32 or both X's dtype: they are taken as float32, the softmax state and the sums are float32 and ``out`` (X's dtype) is
+    rounded once per element; every gradient comes back in its operand's dtype.  Empty rows give 0; duplicates are separate entries.
     One kernel, one pass over the entries; what ``edge_softmax`` + ``spmm_values`` on the composed scores give, without the
     ``[nnz, heads]`` score and probability tensors.  Differentiable in ``a_dst``, ``a_src`` and ``X``: the forward saves only
     node-sized tensors, the backward recomputes the probabilities and runs on ``spmm_values`` and ``pygim_sddmm`` (deterministic; its
     ``[nnz, heads]`` tensors are transient, a fused backward kernel is not part of this).  Runs on the device; CPU tensors are staged
     there and the result comes back to X's device.  No double backward."""
     g = EdgeGraph.of(graph)
-    if X.dtype not in FLOAT_TYPES or a_dst.dtype != X.dtype or a_src.dtype != X.dtype:
-        raise TypeError(f"gat_aggregate: a_dst, a_src and X must all be float32 or float64, got {a_dst.dtype}, {a_src.dtype} and {X.dtype}")
+    if X.dtype in HALF_TYPES:
+        if a_dst.dtype != a_src.dtype or a_dst.dtype not in (torch.float32, X.dtype):
+            raise TypeError(f"gat_aggregate: beside {X.dtype} features a_dst and a_src must both be float32 or both {X.dtype}, "
+                            f"got {a_dst.dtype} and {a_src.dtype}")
+    elif X.dtype not in FLOAT_TYPES or a_dst.dtype != X.dtype or a_src.dtype != X.dtype:
+        raise TypeError(f"gat_aggregate: a_dst, a_src and X must all be float32 or float64 (or X bfloat16 / float16), "
+                        f"got {a_dst.dtype}, {a_src.dtype} and {X.dtype}")
     if a_src.dim() == 1 and a_dst.dim() == 1:
         a_src, a_dst = a_src.unsqueeze(1), a_dst.unsqueeze(1)
     if a_src.dim() != 2 or a_dst.dim() != 2 or a_src.size(1) < 1 or a_dst.size(1) != a_src.size(1):
@@ -319,5 +363,7 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
     if X.size(1) < 1 or X.size(1) % heads != 0:
         raise ValueError(f"gat_aggregate: heads = {heads} must divide h = {X.size(1)}")
     home = X.device
-    out = GatAggregate.apply(g, a_dst.to(g.device).contiguous(), a_src.to(g.device).contiguous(), X.to(g.device).contiguous(), float(negative_slope))
+    ct = _compute_dtype(X.dtype)
+    out = GatAggregate.apply(g, a_dst.to(g.device, ct).contiguous(), a_src.to(g.device, ct).contiguous(), X.to(g.device).contiguous(),
+                             float(negative_slope))
     return out.to(home)

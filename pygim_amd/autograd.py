@@ -62,12 +62,14 @@ def aggregate(A, B: torch.Tensor, value=None):
 def sddmm(rowptr: torch.Tensor, col: torch.Tensor, G: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
     """``out[e] = G[row(e)] . X[col[e]]`` for every stored entry ``e`` of the CSR (rowptr [nrows + 1], col [nnz]), in stored order.
 
-    G [nrows, h] and X [ncols, h] float32 or float64 (the same type).  Runs on the device (pygim_sddmm: hand-written for gfx950,
+    G [nrows, h] and X [ncols, h] float32 or float64 (the same type), or both bfloat16 / both float16: the products and sums are then
+    float32 and so is the result (nothing is rounded to 16 bits).  Runs on the device (pygim_sddmm: hand-written for gfx950,
     no atomics, the same bits on every run); CPU tensors are staged there and the result comes back to G's device."""
     from . import pim_ops
+    from .attention import HALF_TYPES, _compute_dtype, _gather_code
 
-    if G.dtype not in FLOAT_TYPES or X.dtype != G.dtype:
-        raise TypeError(f"sddmm: G and X must both be float32 or float64, got {G.dtype} and {X.dtype}")
+    if G.dtype not in FLOAT_TYPES + HALF_TYPES or X.dtype != G.dtype:
+        raise TypeError(f"sddmm: G and X must both be float32, float64, bfloat16 or float16, got {G.dtype} and {X.dtype}")
     if G.dim() != 2 or X.dim() != 2 or G.size(1) != X.size(1):
         raise ValueError(f"sddmm: G {tuple(G.shape)} and X {tuple(X.shape)} must be [*, h] with the same h")
     nrows, nnz = rowptr.numel() - 1, col.numel()
@@ -86,9 +88,9 @@ def sddmm(rowptr: torch.Tensor, col: torch.Tensor, G: torch.Tensor, X: torch.Ten
             raise ValueError("sddmm: rowptr must rise from 0 to nnz and every column must index a row of X")
     G = G.to(dev).contiguous()
     X = X.to(dev).contiguous()
-    out = torch.empty(nnz, dtype=G.dtype, device=dev)
+    out = torch.empty(nnz, dtype=_compute_dtype(G.dtype), device=dev)
     if nnz > 0:
         stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        pim_ops._lib.sddmm(pim_ops.DTYPE_CODE[G.dtype], nrows, rowptr.data_ptr(), col.data_ptr(), nnz, G.data_ptr(), G.size(1),
+        pim_ops._lib.sddmm(_gather_code(G.dtype), nrows, rowptr.data_ptr(), col.data_ptr(), nnz, G.data_ptr(), G.size(1),
                            X.data_ptr(), X.size(1), G.size(1), out.data_ptr(), stream)
     return out.to(home)

@@ -189,7 +189,8 @@ class SparseGroupBase:
     # -- the product with values given per call (pygim_amd/attention.py) -----------------------------------
     def mul_values(self, value: torch.Tensor, B: torch.Tensor, heads: int = 1):
         """``out[r] = sum_e value[e, head] * B[col[e]]`` on the raw tensor's structure, in its CSR entry order: value [nnz] or
-        [nnz, heads], float32 / float64 like B.  ``mul`` multiplies by the values the group was created with; this is the product for
+        [nnz, heads], float32 / float64 like B (B may also be bfloat16 / float16, value then float32 or B's dtype: float32 sums, one rounding
+        of the result).  ``mul`` multiplies by the values the group was created with; this is the product for
         values that change between calls (no group is created or used).  Differentiable in value and B."""
         from ..attention import EdgeGraph, spmm_values
 
@@ -199,7 +200,7 @@ class SparseGroupBase:
     def mul_reduce(self, B: torch.Tensor, reduce: str):
         """``torch_sparse.matmul(self.raw, B, reduce)`` for ``"mean"``, ``"max"`` or ``"min"`` on the raw tensor's structure, weighted
         by its stored values (cast to B's dtype) when it has them and by ones otherwise.  A reduction other than the sum cannot be
-        compiled into a group: none is created or used.  Differentiable in B (float32 / float64)."""
+        compiled into a group: none is created or used.  Differentiable in B (float32 / float64; ``"mean"`` also takes bfloat16 / float16 B)."""
         from ..reduce import matmul_reduce
 
         return matmul_reduce(self, B, reduce)

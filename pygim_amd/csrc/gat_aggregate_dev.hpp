@@ -48,12 +48,14 @@ inline uint64_t gat_workspace_bytes(uint64_t nnz, uint64_t h, uint64_t heads, si
 
 // WHOLE: the wave is one lane group (L = 64) that holds NV pieces of VEC features per lane; else NV = 1 and L < 64 is a launch argument.
 // lse may be null.  ws: accumulator slots, ws_stat: the (m, l) slots.
-template <typename T, int VEC, int NV, bool WHOLE>
+// S is the storage type of X and out, T the type of a_dst, a_src, lse, (m, l, acc) and the slots (S = T, or a 16-bit S with T = float:
+// an X piece is widened as it is folded, acc / l is rounded once where a finished row is stored).
+template <typename T, typename S, int VEC, int NV, bool WHOLE>
 __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                     const T *__restrict__ a_dst, const T *__restrict__ a_src, uint32_t heads, T slope,
-                                                    const T *__restrict__ X, uint64_t ldx, uint32_t h, uint32_t L, T *__restrict__ out, uint64_t ldo,
+                                                    const S *__restrict__ X, uint64_t ldx, uint32_t h, uint32_t L, S *__restrict__ out, uint64_t ldo,
                                                     T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat) {
-    using V = typename SdVec<T, VEC>::type;
+    using V = typename SdVec<S, VEC>::type;
     constexpr int U = NV == 1 ? RG_U : RG_U / 2;
     if constexpr (WHOLE) L = 64;
     const uint32_t R = 64 / L;
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
             }
             if (grp == 0 && fok[v]) {
                 if (to_slot) {
-                    rg_store<T, VEC>(ws + slots + (slot ? h : 0u) + f[v], acc[v]);
+                    rg_store<T, T, VEC>(ws + slots + (slot ? h : 0u) + f[v], acc[v]);
                     if (first[v]) {
                         T *st = ws_stat + ((wave * 2 + slot) * heads + hv[v]) * 2;
                         st[0] = m[v];
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
                     const T inv = T(1) / l[v];
 #pragma unroll
                     for (int i = 0; i < VEC; i++) acc[v][i] = acc[v][i] * inv;
-                    rg_store<T, VEC>(out + (uint64_t)row * ldo + f[v], acc[v]);
+                    rg_store<S, T, VEC>(out + (uint64_t)row * ldo + f[v], acc[v]);
                     if (lse && first[v]) lse[(uint64_t)row * heads + hv[v]] = m[v] + gat_log(l[v]);
                 }
             }
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
                     const uint32_t kk = k0 + (uint32_t)u * R + grp;
                     ok[u] = kk <= last;
                     const uint32_t col = rg_take32<WHOLE>(my_col, ok[u] ? kk : pos);
-                    const T *xr = X + (uint64_t)col * ldx;
+                    const S *xr = X + (uint64_t)col * ldx;
                     const T *ar = a_src + (uint64_t)col * heads;
 #pragma unroll
                     for (int v = 0; v < NV; v++) {
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
                             const T p = es_exp(s[u][v] - M);
                             l[v] = l[v] + p;
 #pragma unroll
-                            for (int i = 0; i < VEC; i++) acc[v][i] = acc[v][i] + p * rg_get<T, VEC>(x[u][v], i);
+                            for (int i = 0; i < VEC; i++) acc[v][i] = acc[v][i] + p * T(rg_get<S, VEC>(x[u][v], i));
                         }
                 }
             }
@@ -205,9 +207,9 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
 
 // one wave per run: the row that goes on after run w = slot 1 of w merged with slot 0 of every later run the row reaches, in order,
 // then divided by its l
-template <typename T>
+template <typename T, typename S>
 __global__ __launch_bounds__(256) void k_gat_fixup(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t nnz, uint32_t h, uint32_t heads,
-                                                   const T *__restrict__ ws, const T *__restrict__ ws_stat, T *__restrict__ out, uint64_t ldo,
+                                                   const T *__restrict__ ws, const T *__restrict__ ws_stat, S *__restrict__ out, uint64_t ldo,
                                                    T *__restrict__ lse) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -231,57 +233,57 @@ __global__ __launch_bounds__(256) void k_gat_fixup(const uint32_t *__restrict__ 
             acc = acc * a + ws[j * 2 * (uint64_t)h + f] * b;
             m = M;
         }
-        out[(uint64_t)row * ldo + f] = acc * (T(1) / l);
+        out[(uint64_t)row * ldo + f] = S(acc * (T(1) / l));
         if (lse && f == k * hd) lse[(uint64_t)row * heads + k] = m + gat_log(l);
     }
 }
 
 // rows without entries: out = 0, lse = 0
-template <typename T>
-__global__ __launch_bounds__(256) void k_gat_empty(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t h, uint32_t heads, T *__restrict__ out,
+template <typename T, typename S>
+__global__ __launch_bounds__(256) void k_gat_empty(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t h, uint32_t heads, S *__restrict__ out,
                                                    uint64_t ldo, T *__restrict__ lse) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= nrows || rowptr[row] != rowptr[row + 1]) return;
-    for (uint32_t f = lane; f < h; f += 64) out[row * ldo + f] = T(0);
+    for (uint32_t f = lane; f < h; f += 64) out[row * ldo + f] = S(0);
     if (lse)
         for (uint32_t k = lane; k < heads; k += 64) lse[row * heads + k] = T(0);
 }
 
-template <typename T, int VEC>
+template <typename T, typename S, int VEC>
 inline void launch_gat_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
-                                T slope, const T *X, uint64_t ldx, uint32_t h, T *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, hipStream_t st) {
+                                T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
     const uint32_t pieces = (h + VEC - 1) / VEC;
     if (pieces <= 32) {
         uint32_t L = 1;
         while (L < pieces) L <<= 1;
-        hipLaunchKernelGGL((k_gat_gather<T, VEC, 1, false>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, L,
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, L,
                            out, ldo, lse, ws, ws_stat);
     } else if (pieces <= 64) {
-        hipLaunchKernelGGL((k_gat_gather<T, VEC, 1, true>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, true>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
                            out, ldo, lse, ws, ws_stat);
     } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_gat_gather<T, VEC, 2, true>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
                            slope, X, ldx, h, 64u, out, ldo, lse, ws, ws_stat);
     }
 }
 
-// 16-byte pieces under the conditions of launch_row_gather: aligned rows of X and out, and no piece across two heads
-template <typename T>
+// 16-byte pieces (of the storage type) under the conditions of launch_row_gather: aligned rows of X and out, and no piece across two heads
+template <typename T, typename S = T>
 inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
-                                 T slope, const T *X, uint64_t ldx, uint32_t h, T *out, uint64_t ldo, T *lse, void *workspace, hipStream_t st) {
-    constexpr uint32_t V = 16 / sizeof(T);
-    if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
+                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, void *workspace, hipStream_t st) {
+    constexpr uint32_t V = 16 / sizeof(S);
+    if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
     const bool vec = (h / heads) % V == 0 && ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_gat_gather_v<T, (int)V>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
-    else launch_gat_gather_v<T, 1>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
+    if (vec) launch_gat_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
+    else launch_gat_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
-        hipLaunchKernelGGL((k_gat_fixup<T>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);
+        hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);
 }
 
 }  // namespace pygim

@@ -611,6 +611,24 @@ template <bool INTS = false, typename F> static void with_elem_type(int dtype, F
 
 static bool is_float_type(int dtype) { return dtype == PYGIM_FLT32 || dtype == PYGIM_DBL64; }
 
+// The gather family (sddmm, spmm_values, gat_aggregate, spmm_reduce MEAN) also takes 16-bit features: X / G / out are stored as
+// PYGIM_FLT16 or PYGIM_BF16 while values, a_dst, a_src, lse, the sddmm result and the workspace slots are float32.  dtype_size() stays 0 for
+// the two codes (group creation and every other entry point reject them through it); these entry points ask here instead.
+static bool is_half_type(int dtype) { return dtype == PYGIM_FLT16 || dtype == PYGIM_BF16; }
+static bool is_gather_type(int dtype) { return is_float_type(dtype) || is_half_type(dtype); }
+// bytes of an element of X / out, and of everything that is computed (values, partials, slots)
+static size_t gather_storage_size(int dtype) { return is_half_type(dtype) ? 2 : dtype_size(dtype); }
+static size_t gather_compute_size(int dtype) { return is_half_type(dtype) ? sizeof(float) : dtype_size(dtype); }
+// f(T(), S()) with T the compute and S the storage type of `dtype` (is_gather_type: the caller has checked it)
+template <typename F> static void with_gather_types(int dtype, F &&f) {
+    switch (dtype) {
+        case PYGIM_FLT16: return f(float(), _Float16());
+        case PYGIM_BF16: return f(float(), __bf16());
+        case PYGIM_FLT32: return f(float(), float());
+        default: return f(double(), double());
+    }
+}
+
 // a pointer argument: checked when the call will use it (`used`: rows > 0, nnz > 0, ...) -- not null unless `optional`, and device memory
 struct PtrArg {
     const void *p;
@@ -639,15 +657,16 @@ extern "C" {
 int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *G, int64_t ldg,
                 const void *X, int64_t ldx, int64_t h, void *out, void *stream) {
     if (int rc = need_init()) return rc;
-    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "sddmm: type must be FLT32 or DBL64");
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "sddmm: type must be FLT32, DBL64, FLT16 or BF16");
     if (int rc = check_csr_call("sddmm", "rowptr / colind / G / X / out", nrows, nnz, 0xFFFFFFFFll - SD_EPW, h, 0xFFFFFFFFll, ldg, ldx,
                                 {{rowptr, true}, {colind, nnz > 0}, {G, nnz > 0}, {X, nnz > 0}, {out, nnz > 0}}))
         return rc;
     if (nnz == 0) return 0;
-    with_elem_type(dtype, [&](auto t) {
+    with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
-        launch_sddmm<T>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)G, (uint64_t)ldg, (const T *)X,
-                        (uint64_t)ldx, (uint32_t)h, (T *)out, (hipStream_t)stream);
+        using S = decltype(s);
+        launch_sddmm<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)G, (uint64_t)ldg, (const S *)X,
+                           (uint64_t)ldx, (uint32_t)h, (T *)out, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
@@ -656,8 +675,8 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
 int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
     (void)heads;
-    if (!is_float_type(dtype) || nnz < 0 || h < 1) return -1;
-    return (int64_t)row_gather_slot_bytes((uint64_t)nnz, (uint64_t)h, dtype_size(dtype));
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1) return -1;
+    return (int64_t)row_gather_slot_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
 }
 
 int64_t pygim_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t heads) {
@@ -669,17 +688,18 @@ int64_t pygim_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int6
 int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, int64_t heads,
                       const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32 or DBL64");
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "spmm_values: heads must divide h");
     if (int rc = check_csr_call("spmm_values", "rowptr / colind / values / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {colind, nnz > 0}, {values, nnz > 0}, {X, nnz > 0}},
                                 pygim_spmm_values_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
-    with_elem_type(dtype, [&](auto t) {
+    with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
-        launch_row_gather<T, FoldSum<false>>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values,
-                                             (uint32_t)heads, (const T *)X, (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, nullptr, workspace,
-                                             (hipStream_t)stream);
+        using S = decltype(s);
+        launch_row_gather<T, FoldSum<false>, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values,
+                                                (uint32_t)heads, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out, (uint64_t)ldo, nullptr, workspace,
+                                                (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
@@ -687,25 +707,26 @@ int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int
 
 int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
-    if (!is_float_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0) return -1;
-    return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, dtype_size(dtype));
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0) return -1;
+    return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
 }
 
 int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
                         int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
                         int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32 or DBL64");
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: heads must divide h");
     if (int rc = check_csr_call("gat_aggregate", "rowptr / colind / a_dst / a_src / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {a_dst, nnz > 0}, {a_src, nnz > 0}, {X, nnz > 0}},
                                 pygim_gat_aggregate_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
-    with_elem_type(dtype, [&](auto t) {
+    with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
-        launch_gat_aggregate<T>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
-                                (uint32_t)heads, (T)negative_slope, (const T *)X, (uint64_t)ldx, (uint32_t)h, (T *)out, (uint64_t)ldo, (T *)lse, workspace,
-                                (hipStream_t)stream);
+        using S = decltype(s);
+        launch_gat_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
+                                   (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace,
+                                   (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
@@ -748,25 +769,37 @@ int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr,
 }
 
 int64_t pygim_spmm_reduce_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
-    if (dtype_size(dtype) == 0 || (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)) return -1;
-    if (op == PYGIM_REDUCE_MEAN && !is_float_type(dtype)) return -1;
+    if (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN) return -1;
+    if (op == PYGIM_REDUCE_MEAN ? !is_gather_type(dtype) : dtype_size(dtype) == 0) return -1;   // 16-bit features: the mean only
     if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll) return -1;
-    return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, dtype_size(dtype));
+    return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
 }
 
 int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values, const void *X,
                       int64_t ldx, int64_t h, void *out, int64_t ldo, int32_t *arg, void *workspace, int64_t workspace_bytes, void *stream) {
     if (int rc = need_init()) return rc;
-    if (dtype_size(dtype) == 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: unknown element type");
+    if (dtype_size(dtype) == 0 && !is_half_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: unknown element type");
     if (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN)
         return fail(PYGIM_ERR_INVALID, "spmm_reduce: op must be PYGIM_REDUCE_MEAN, _MAX or _MIN (sums: pygim_spmm_values, pygim_spmm_run_group)");
-    if (op == PYGIM_REDUCE_MEAN && !is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean needs FLT32 or DBL64");
+    if (op == PYGIM_REDUCE_MEAN && !is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean needs FLT32, DBL64, FLT16 or BF16");
+    if (op != PYGIM_REDUCE_MEAN && is_half_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: max / min take no 16-bit type (FLT16 / BF16: mean only)");
     if (op == PYGIM_REDUCE_MEAN && arg) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean has no arg output");
     if (arg && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: arg must be 4-byte aligned");
     if (int rc = check_csr_call("spmm_reduce", "rowptr / colind / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {arg, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {values, nnz > 0, true}},
                                 pygim_spmm_reduce_workspace(dtype, op, nrows, nnz, h), workspace, workspace_bytes))
         return rc;
+    if (is_half_type(dtype)) {   // the mean alone: float32 values (or none), float32 sums and division, one rounding into out
+        const uint32_t *rp = (const uint32_t *)rowptr, *ci = (const uint32_t *)colind;
+        if (dtype == PYGIM_BF16)
+            launch_spmm_mean16<__bf16>(rp, ci, (uint32_t)nrows, (uint32_t)nnz, (const float *)values, (const __bf16 *)X, (uint64_t)ldx, (uint32_t)h,
+                                       (__bf16 *)out, (uint64_t)ldo, workspace, (hipStream_t)stream);
+        else
+            launch_spmm_mean16<_Float16>(rp, ci, (uint32_t)nrows, (uint32_t)nnz, (const float *)values, (const _Float16 *)X, (uint64_t)ldx, (uint32_t)h,
+                                         (_Float16 *)out, (uint64_t)ldo, workspace, (hipStream_t)stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     with_elem_type<true>(dtype, [&](auto t) {
         using T = decltype(t);
         launch_spmm_reduce<T>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)values, (const T *)X,

@@ -80,14 +80,22 @@ template <typename T, int VEC> __device__ inline T rg_get(const typename SdVec<T
     else return v[i];
 }
 
-template <typename T, int VEC> __device__ inline void rg_store(T *dst, const T *a) {
+// VEC elements of the compute type T, stored as D: D = T (a workspace slot, or out when storage and compute type are one), or the
+// 16-bit storage type of out -- the one place a result is rounded (round-to-nearest-even; v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).
+// A piece of 8 float32 partials is 32 bytes in a slot whose rows are 16-byte aligned: stored with that alignment.
+template <typename D, int VEC> struct RgPiece { typedef D __attribute__((ext_vector_type(VEC), aligned(sizeof(D) * VEC < 16 ? sizeof(D) * VEC : 16))) type; };
+template <typename D> struct RgPiece<D, 1> { typedef D type; };
+
+template <typename D, typename T, int VEC> __device__ inline void rg_store(D *dst, const T *a) {
     typename SdVec<T, VEC>::type v;
     if constexpr (VEC == 1) v = a[0];
     else {
 #pragma unroll
         for (int i = 0; i < VEC; i++) v[i] = a[i];
     }
-    *(typename SdVec<T, VEC>::type *)dst = v;
+    if constexpr (std::is_same<D, T>::value) *(typename RgPiece<T, VEC>::type *)dst = v;
+    else if constexpr (VEC == 1) *dst = D(v);
+    else *(typename RgPiece<D, VEC>::type *)dst = __builtin_convertvector(v, typename SdVec<D, VEC>::type);
 }
 
 // entry indices of VEC features; `final`: RD_NONE (no entry won) becomes -1
@@ -119,12 +127,15 @@ template <bool MEAN_> struct FoldSum {
 
 // WHOLE: the wave is one lane group (L = 64) that holds NV pieces of VEC features per lane; else NV = 1 and L < 64 is a launch argument.
 // values (folds with one weight per entry), arg: may be null (unit weights; no index output).  ws_idx: the index half of the workspace.
-template <typename T, int VEC, int NV, bool WHOLE, typename Fold>
+// S is the storage type of X and out, T the type of everything else (values, accumulators, the xor tree, the slots).  S = T for the six
+// element types; S = _Float16 / __bf16 with T = float for 16-bit features: an X piece is widened as it is folded (exact) and a finished
+// row is rounded once, where it is stored into out.
+template <typename T, typename S, int VEC, int NV, bool WHOLE, typename Fold>
 __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
-                                                    const T *__restrict__ values, uint32_t heads, const T *__restrict__ X, uint64_t ldx, uint32_t h,
-                                                    uint32_t L, T *__restrict__ out, uint64_t ldo, int32_t *__restrict__ arg, T *__restrict__ ws,
+                                                    const T *__restrict__ values, uint32_t heads, const S *__restrict__ X, uint64_t ldx, uint32_t h,
+                                                    uint32_t L, S *__restrict__ out, uint64_t ldo, int32_t *__restrict__ arg, T *__restrict__ ws,
                                                     int32_t *__restrict__ ws_idx) {
-    using V = typename SdVec<T, VEC>::type;
+    using V = typename SdVec<S, VEC>::type;
     constexpr int U = NV == 1 ? RG_U : RG_U / 2;
     constexpr int NW = Fold::PER_HEAD ? NV : 1;   // weights held per entry in flight
     if constexpr (WHOLE) L = 64;
@@ -161,7 +172,12 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
     };
     // join the lane groups, then store: into the workspace slot (raw partial), or the finished row `row` into out / arg
     const auto flush = [&](bool to_slot, uint32_t slot, uint32_t row) {
-        T *dst = to_slot ? ws + slots + (slot ? h : 0u) : out + (uint64_t)row * ldo;
+        // one destination when a slot and out hold the same type; else the slot (T) or the row of out (S, rounded by the store)
+        T *dst = nullptr;
+        S *dst_out = nullptr;
+        if constexpr (std::is_same<S, T>::value) dst = to_slot ? ws + slots + (slot ? h : 0u) : out + (uint64_t)row * ldo;
+        else if (to_slot) dst = ws + slots + (slot ? h : 0u);
+        else dst_out = out + (uint64_t)row * ldo;
         int32_t *dst_i = nullptr;
         if constexpr (Fold::INDEXED) dst_i = to_slot ? ws_idx + slots + (slot ? h : 0u) : (arg ? arg + (uint64_t)row * h : nullptr);
         T cnt = T(1);
@@ -186,7 +202,8 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
                         for (int i = 0; i < VEC; i++) acc[v][i] = acc[v][i] / cnt;
                     }
                 }
-                rg_store<T, VEC>(dst + f[v], acc[v]);
+                if (std::is_same<S, T>::value || to_slot) rg_store<T, T, VEC>(dst + f[v], acc[v]);
+                else rg_store<S, T, VEC>(dst_out + f[v], acc[v]);
                 if constexpr (Fold::INDEXED)
                     if (dst_i) rg_store_idx<VEC>(dst_i + f[v], aidx[v], !to_slot);
             }
@@ -224,7 +241,7 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
                     ei[u] = (int32_t)(base + kk);
                     const uint32_t col = rg_take32<WHOLE>(my_col, ok[u] ? kk : pos);
                     const T wv = rg_take<WHOLE, T>(my_val, ok[u] ? kk : pos);
-                    const T *xr = X + (uint64_t)col * ldx;
+                    const S *xr = X + (uint64_t)col * ldx;
 #pragma unroll
                     for (int v = 0; v < NV; v++) {
                         x[u][v] = V(0);
@@ -243,7 +260,7 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
                         if (ok[u] && fok[v]) {
 #pragma unroll
                             for (int i = 0; i < VEC; i++)
-                                Fold::join(acc[v][i], aidx[v][i], rd_mul<T>(w[u][v < NW ? v : 0], rg_get<T, VEC>(x[u][v], i)), ei[u]);
+                                Fold::join(acc[v][i], aidx[v][i], rd_mul<T>(w[u][v < NW ? v : 0], T(rg_get<S, VEC>(x[u][v], i))), ei[u]);
                         }
                 }
             }
@@ -261,9 +278,9 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
 }
 
 // one wave per run: the row that goes on after run w = slot 1 of w joined with slot 0 of every later run the row reaches, in order
-template <typename T, typename Fold>
+template <typename T, typename S, typename Fold>
 __global__ __launch_bounds__(256) void k_row_gather_fixup(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t nnz, uint32_t h,
-                                                          const T *__restrict__ ws, const int32_t *__restrict__ ws_idx, T *__restrict__ out, uint64_t ldo,
+                                                          const T *__restrict__ ws, const int32_t *__restrict__ ws_idx, S *__restrict__ out, uint64_t ldo,
                                                           int32_t *__restrict__ arg) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -286,7 +303,7 @@ __global__ __launch_bounds__(256) void k_row_gather_fixup(const uint32_t *__rest
             Fold::join(s, si, ws[at], oi);
         }
         if constexpr (Fold::MEAN) s = s / T(re - rb);
-        out[(uint64_t)row * ldo + f] = s;
+        out[(uint64_t)row * ldo + f] = S(s);
         if constexpr (Fold::INDEXED)
             if (arg) arg[(uint64_t)row * h + f] = si == RD_NONE ? -1 : si;
     }
@@ -310,41 +327,42 @@ inline uint64_t row_gather_runs(uint64_t nnz) { return (nnz + RG_EPW - 1) / RG_E
 inline uint64_t row_gather_slot_bytes(uint64_t nnz, uint64_t h, size_t elem) { return row_gather_runs(nnz) * 2 * h * elem; }
 inline uint64_t row_gather_index_offset(uint64_t nnz, uint64_t h, size_t elem) { return (row_gather_slot_bytes(nnz, h, elem) + 15) / 16 * 16; }
 
-template <typename T, int VEC, typename Fold>
-inline void launch_row_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const T *X,
-                                uint64_t ldx, uint32_t h, T *out, uint64_t ldo, int32_t *arg, T *ws, int32_t *ws_idx, hipStream_t st) {
+template <typename T, typename S, int VEC, typename Fold>
+inline void launch_row_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const S *X,
+                                uint64_t ldx, uint32_t h, S *out, uint64_t ldo, int32_t *arg, T *ws, int32_t *ws_idx, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
     const uint32_t pieces = (h + VEC - 1) / VEC;
     if (pieces <= 32) {
         uint32_t L = 1;
         while (L < pieces) L <<= 1;
-        hipLaunchKernelGGL((k_row_gather<T, VEC, 1, false, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, L, out,
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, false, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, L, out,
                            ldo, arg, ws, ws_idx);
     } else if (pieces <= 64) {
-        hipLaunchKernelGGL((k_row_gather<T, VEC, 1, true, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, 64u, out,
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, true, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, 64u, out,
                            ldo, arg, ws, ws_idx);
     } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_row_gather<T, VEC, 2, true, Fold>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 2, true, Fold>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
                            heads, X, ldx, h, 64u, out, ldo, arg, ws, ws_idx);
     }
 }
 
 // 16-byte pieces when every row of X and out starts 16-byte aligned, h fills whole pieces and no piece lies across two heads (arg and
-// the index slots are stored with 4-byte alignment, whatever their width).  heads: 1 unless Fold::PER_HEAD.
-template <typename T, typename Fold>
-inline void launch_row_gather(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const T *X,
-                              uint64_t ldx, uint32_t h, T *out, uint64_t ldo, int32_t *arg, void *workspace, hipStream_t st) {
-    constexpr uint32_t V = 16 / sizeof(T);
-    if (nrows > 0) hipLaunchKernelGGL((k_row_gather_empty<T>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, out, ldo, arg);
+// the index slots are stored with 4-byte alignment, whatever their width).  heads: 1 unless Fold::PER_HEAD.  A piece is 16 bytes of the
+// STORAGE type: 8 features of a 16-bit one (h = 256: 32 pieces, two entries side by side in a wave instruction).
+template <typename T, typename Fold, typename S = T>
+inline void launch_row_gather(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const S *X,
+                              uint64_t ldx, uint32_t h, S *out, uint64_t ldo, int32_t *arg, void *workspace, hipStream_t st) {
+    constexpr uint32_t V = 16 / sizeof(S);
+    if (nrows > 0) hipLaunchKernelGGL((k_row_gather_empty<S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, out, ldo, arg);
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     int32_t *ws_idx = Fold::INDEXED ? (int32_t *)((char *)workspace + row_gather_index_offset(nnz, h, sizeof(T))) : nullptr;
     const bool vec = (h / heads) % V == 0 && ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_row_gather_v<T, (int)V, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
-    else launch_row_gather_v<T, 1, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
+    if (vec) launch_row_gather_v<T, S, (int)V, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
+    else launch_row_gather_v<T, S, 1, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
-        hipLaunchKernelGGL((k_row_gather_fixup<T, Fold>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, ws, ws_idx, out, ldo, arg);
+        hipLaunchKernelGGL((k_row_gather_fixup<T, S, Fold>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, ws, ws_idx, out, ldo, arg);
 }
 
 }  // namespace pygim

@@ -35,14 +35,15 @@ __device__ inline uint32_t sd_row_of(const uint32_t *__restrict__ rowptr, uint32
 template <typename T, int VEC> struct SdVec { typedef T __attribute__((ext_vector_type(VEC))) type; };
 template <typename T> struct SdVec<T, 1> { typedef T type; };
 
-template <typename T, int VEC>
-__device__ inline T sd_dot(const typename SdVec<T, VEC>::type &a, const typename SdVec<T, VEC>::type &b) {
+// a . b in T, the operands stored as S (widened element by element: exact)
+template <typename T, typename S, int VEC>
+__device__ inline T sd_dot(const typename SdVec<S, VEC>::type &a, const typename SdVec<S, VEC>::type &b) {
     if constexpr (VEC == 1) {
-        return a * b;
+        return T(a) * T(b);
     } else {
-        T s = a[0] * b[0];
+        T s = T(a[0]) * T(b[0]);
 #pragma unroll
-        for (int i = 1; i < VEC; i++) s += a[i] * b[i];
+        for (int i = 1; i < VEC; i++) s += T(a[i]) * T(b[i]);
         return s;
     }
 }
@@ -54,10 +55,11 @@ template <int L> __device__ inline uint32_t sd_take(uint32_t v, uint32_t src) {
 }
 
 // NVC: 16-byte pieces per lane held at once (features per lane and pass = NVC * VEC; wider rows take several passes)
-template <typename T, int VEC, int L, int NVC>
+// S is the storage type of G and X, T the type of the products, the sums and out (S = T, or a 16-bit S with T = float: no rounding)
+template <typename T, typename S, int VEC, int L, int NVC>
 __global__ __launch_bounds__(256) void k_sddmm(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
-                                               const T *__restrict__ G, uint64_t ldg, const T *__restrict__ X, uint64_t ldx, uint32_t h, T *__restrict__ out) {
-    using V = typename SdVec<T, VEC>::type;
+                                               const S *__restrict__ G, uint64_t ldg, const S *__restrict__ X, uint64_t ldx, uint32_t h, T *__restrict__ out) {
+    using V = typename SdVec<S, VEC>::type;
     constexpr int R = 64 / L;   // entries side by side per wave-instruction
     const uint32_t lane = threadIdx.x & 63, grp = lane / L, li = lane % L;
     const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(256) void k_sddmm(const uint32_t *__restrict__ rowp
         for (uint32_t c0 = 0; c0 < nv; c0 += NVC) {
             V gv[NVC];
             if (one_row) {
-                const T *gr = G + (uint64_t)row * ldg;
+                const S *gr = G + (uint64_t)row * ldg;
 #pragma unroll
                 for (int v = 0; v < NVC; v++) {
                     const uint32_t f = ((c0 + v) * L + li) * VEC;
@@ -93,15 +95,15 @@ __global__ __launch_bounds__(256) void k_sddmm(const uint32_t *__restrict__ rowp
                 const uint32_t src = grp + (uint32_t)(R * k);
                 const bool valid = base + src < bend;
                 const uint32_t col = sd_take<L>(my_col, src);
-                const T *xr = X + (uint64_t)col * ldx;
-                const T *gr = G + (uint64_t)(one_row ? row : sd_take<L>(my_row, src)) * ldg;
+                const S *xr = X + (uint64_t)col * ldx;
+                const S *gr = G + (uint64_t)(one_row ? row : sd_take<L>(my_row, src)) * ldg;
 #pragma unroll
                 for (int v = 0; v < NVC; v++) {
                     const uint32_t f = ((c0 + v) * L + li) * VEC;
                     if (valid && c0 + v < nv && f < h) {
                         const V xv = *(const V *)(xr + f);
                         const V gg = one_row ? gv[v] : *(const V *)(gr + f);
-                        p[k] += sd_dot<T, VEC>(gg, xv);
+                        p[k] += sd_dot<T, S, VEC>(gg, xv);
                     }
                 }
             }
@@ -123,35 +125,35 @@ __global__ __launch_bounds__(256) void k_sddmm(const uint32_t *__restrict__ rowp
     }
 }
 
-template <typename T, int VEC, int L>
-inline void launch_sddmm_l(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+template <typename T, typename S, int VEC, int L>
+inline void launch_sddmm_l(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *G, uint64_t ldg, const S *X, uint64_t ldx,
                            uint32_t h, T *out, hipStream_t st) {
     const uint64_t waves = ((uint64_t)nnz + SD_EPW - 1) / SD_EPW;
     // pieces held at once: the whole row up to 4 pieces (h = 256 FLT32 / DBL64 with 64 lanes: 1 / 2), longer rows in passes of 4
-    hipLaunchKernelGGL((k_sddmm<T, VEC, L, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out);
+    hipLaunchKernelGGL((k_sddmm<T, S, VEC, L, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out);
 }
 
-template <typename T, int VEC>
-inline void launch_sddmm_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+template <typename T, typename S, int VEC>
+inline void launch_sddmm_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *G, uint64_t ldg, const S *X, uint64_t ldx,
                            uint32_t h, T *out, hipStream_t st) {
     const uint32_t pieces = (h + VEC - 1) / VEC;
-    if (pieces <= 1) launch_sddmm_l<T, VEC, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 2) launch_sddmm_l<T, VEC, 2>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 4) launch_sddmm_l<T, VEC, 4>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 8) launch_sddmm_l<T, VEC, 8>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 16) launch_sddmm_l<T, VEC, 16>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 32) launch_sddmm_l<T, VEC, 32>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else launch_sddmm_l<T, VEC, 64>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    if (pieces <= 1) launch_sddmm_l<T, S, VEC, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 2) launch_sddmm_l<T, S, VEC, 2>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 4) launch_sddmm_l<T, S, VEC, 4>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 8) launch_sddmm_l<T, S, VEC, 8>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 16) launch_sddmm_l<T, S, VEC, 16>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (pieces <= 32) launch_sddmm_l<T, S, VEC, 32>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else launch_sddmm_l<T, S, VEC, 64>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
 }
 
-// 16-byte pieces when every row of G and X starts 16-byte aligned and h fills whole pieces; else one element per lane
-template <typename T>
-inline void launch_sddmm(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *G, uint64_t ldg, const T *X, uint64_t ldx,
+// 16-byte pieces (of the storage type) when every row of G and X starts 16-byte aligned and h fills whole pieces; else one element per lane
+template <typename T, typename S = T>
+inline void launch_sddmm(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *G, uint64_t ldg, const S *X, uint64_t ldx,
                          uint32_t h, T *out, hipStream_t st) {
-    constexpr uint32_t V = 16 / sizeof(T);
+    constexpr uint32_t V = 16 / sizeof(S);
     const bool vec = h % V == 0 && ldg % V == 0 && ldx % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)X % 16 == 0;
-    if (vec) launch_sddmm_v<T, (int)V>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else launch_sddmm_v<T, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    if (vec) launch_sddmm_v<T, S, (int)V>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else launch_sddmm_v<T, S, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
 }
 
 }  // namespace pygim

@@ -56,6 +56,13 @@ inline uint64_t spmm_reduce_workspace_bytes(int op, uint64_t nnz, uint64_t h, si
     return row_gather_index_offset(nnz, h, elem) + (op == RD_MEAN ? 0 : row_gather_slot_bytes(nnz, h, sizeof(int32_t)));
 }
 
+// the mean of 16-bit features (S = _Float16 / __bf16): float32 values, sums, slots and division; the quotient is rounded once into out
+template <typename S>
+inline void launch_spmm_mean16(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const float *values, const S *X, uint64_t ldx,
+                               uint32_t h, S *out, uint64_t ldo, void *workspace, hipStream_t st) {
+    launch_row_gather<float, FoldSum<true>, S>(rowptr, colind, nrows, nnz, values, 1u, X, ldx, h, out, ldo, nullptr, workspace, st);
+}
+
 // op: RD_MEAN (floating types only: the caller checks), RD_MAX or RD_MIN
 template <typename T>
 inline void launch_spmm_reduce(int op, const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, const T *X, uint64_t ldx,
@@ -132,7 +139,7 @@ __global__ __launch_bounds__(256) void k_spmm_reduce_bwd(const uint32_t *__restr
     }
 #pragma unroll
     for (int v = 0; v < NV; v++)
-        if (fok[v]) rg_store<T, VEC>(dX + c * ldd + f[v], acc[v]);
+        if (fok[v]) rg_store<T, T, VEC>(dX + c * ldd + f[v], acc[v]);
 }
 
 template <typename T, int VEC>

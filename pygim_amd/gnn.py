@@ -13,7 +13,8 @@ SparseTensor (cpu path), a backend_pim SparseTensorCOO, or a pygim_amd.dist.RowS
 x and the result are then this rank's row block).
 
 GATConv / GAT are the attention layer on top of pygim_amd.attention: its edge weights are computed on every call, so its aggregation
-is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values frozen in the group); float32 / float64, trainable.
+is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values frozen in the group); float32 / float64, trainable, and
+bfloat16 / float16 features after ``model.to(torch.bfloat16)`` or under ``torch.autocast`` (so is ``SAGEConv(aggr="mean")``).
 ``GATConv(..., fused=True)`` / ``GAT(..., fused=True)`` aggregate with ``gat_aggregate`` instead: scores, softmax and product in one
 kernel, no ``[nnz, heads]`` tensor written or kept for the backward.  The default (``fused=False``) is the layer as before.
 """
@@ -98,6 +99,8 @@ class GATConv(torch.nn.Module):
         else:
             row, col = g.row.long().to(x.device), g.col.long().to(x.device)
             score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
+            if score.dtype in (torch.float16, torch.bfloat16):   # edge_softmax is float32 / float64: 16-bit scores go up, and
+                score = score.float()                             # spmm_values takes the float32 probabilities beside 16-bit features
             p = edge_softmax(g, score)
             out = spmm_values(g, p, xp.reshape(-1, H * F_), heads=H)
         if not self.concat:

@@ -6,7 +6,8 @@ like ``spmm_values`` (pygim_spmm_reduce, pygim_spmm_reduce_backward: hand-writte
 run).  Sums stay with ``mul`` / ``spmm_values``.
 
 * mean: the sum divided by the row's number of stored entries (duplicates count; not the sum of the values); float32 / float64;
-  differentiable in X and value (``spmm_values`` on the transposed structure, ``pygim_sddmm``).
+  differentiable in X and value (``spmm_values`` on the transposed structure, ``pygim_sddmm``).  X may also be bfloat16 / float16
+  (value float32 or X's dtype, taken as float32): float32 sums and division, the quotient rounded once into X's dtype.
 * max / min: all six element types; among equal products the lowest entry index wins and ``return_arg`` hands out that index per
   (row, feature), -1 for empty rows; differentiable in X (float32 / float64): the gradient goes to the entry that won.
 
@@ -18,21 +19,22 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from .attention import FLOAT_TYPES, EdgeGraph, _backend, _run_spmm_values, _stream, _workspace
+from .attention import FLOAT_TYPES, HALF_TYPES, EdgeGraph, _backend, _compute_dtype, _gather_code, _run_spmm_values, _stream, _workspace
 
 REDUCE_CODE = {"mean": 1, "max": 2, "min": 3}   # PYGIM_REDUCE_*
 
 
 def _run_spmm_reduce(g: EdgeGraph, value, X: torch.Tensor, op: int, want_arg: bool):
-    """value [nnz] or None and X [ncols, h] contiguous on g.device -> (out [nrows, h], arg int32 [nrows, h] or None)"""
-    L, code = _backend()
+    """value [nnz] (float32 beside 16-bit X) or None and X [ncols, h] contiguous on g.device -> (out [nrows, h], arg int32 [nrows, h] or None)"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
     h = X.size(1)
     out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
     arg = torch.empty((g.nrows, h), dtype=torch.int32, device=g.device) if want_arg else None
     if g.nrows == 0:
         return out, arg
-    ws = _workspace(L.spmm_reduce_workspace(code[X.dtype], op, g.nrows, g.nnz, h), g.device)
-    L.spmm_reduce(code[X.dtype], op, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, 0 if value is None else value.data_ptr(), X.data_ptr(),
+    ws = _workspace(L.spmm_reduce_workspace(dt, op, g.nrows, g.nnz, h), g.device)
+    L.spmm_reduce(dt, op, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, 0 if value is None else value.data_ptr(), X.data_ptr(),
                   X.stride(0), h, out.data_ptr(), h, 0 if arg is None else arg.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device))
     return out, arg
 
@@ -62,7 +64,8 @@ class SpmmMean(torch.autograd.Function):
     def backward(ctx, G):
         g = ctx.g
         value, X = ctx.saved_tensors
-        cnt = _counts(g, X.dtype)
+        ct = _compute_dtype(X.dtype)   # float32 beside 16-bit X and G: counts and weights are never held in 16 bits
+        cnt = _counts(g, ct)
         dvalue = dX = None
         if ctx.needs_input_grad[2]:   # A_mean^T . G: the sum kernel on the transposed structure with values w / count
             gt, perm = g.transposed()
@@ -71,12 +74,15 @@ class SpmmMean(torch.autograd.Function):
                 w = w * value
             dX = _run_spmm_values(gt, w.index_select(0, perm).unsqueeze(1).contiguous(), G.contiguous(), 1)
         if value is not None and ctx.needs_input_grad[1]:
-            L, code = _backend()
-            dvalue = torch.empty(g.nnz, dtype=X.dtype, device=g.device)
+            L, _ = _backend()
+            dvalue = torch.empty(g.nnz, dtype=ct, device=g.device)
             if g.nnz > 0:
-                Gc = (G / cnt.unsqueeze(1)).contiguous()
-                L.sddmm(code[X.dtype], g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Gc.data_ptr(), Gc.size(1), X.data_ptr(), X.stride(0),
+                # 16-bit G: the dot products of G itself (float32 out), divided afterwards -- G / count would be rounded to 16 bits
+                Gc = G.contiguous() if X.dtype in HALF_TYPES else (G / cnt.unsqueeze(1)).contiguous()
+                L.sddmm(_gather_code(X.dtype), g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Gc.data_ptr(), Gc.size(1), X.data_ptr(), X.stride(0),
                         X.size(1), dvalue.data_ptr(), _stream(g.device))
+                if X.dtype in HALF_TYPES:
+                    dvalue.div_(cnt.index_select(0, g.row.long()))
         return None, dvalue, dX
 
 
@@ -113,8 +119,9 @@ class SpmmArgReduce(torch.autograd.Function):
 def spmm_reduce(graph, X: torch.Tensor, reduce: str, value=None, return_arg: bool = False):
     """``out[r, f] = REDUCE over the stored entries e of row r of value[e] * X[col[e], f]`` (unit weights without ``value``)
 
-    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; X [columns, h]; reduce: ``"mean"`` (float32 / float64) or
-    ``"max"`` / ``"min"`` (any of the six element types); value [nnz] in X's dtype, in CSR entry order.  Empty rows give 0.
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; X [columns, h]; reduce: ``"mean"`` (float32 / float64, or
+    bfloat16 / float16 features: float32 arithmetic, one rounding of the result) or ``"max"`` / ``"min"`` (any of the six element
+    types; no 16-bit floats); value [nnz] in X's dtype (float32 or X's dtype beside 16-bit X), in CSR entry order.  Empty rows give 0.
     ``return_arg`` (max / min): also the int32 [rows, h] index of the entry that won, -1 for empty rows; ties go to the lowest index.
     Differentiable in X (and in value for mean) for float types.  Runs on the device; CPU tensors are staged there and the results
     come back to X's device."""
@@ -123,12 +130,13 @@ def spmm_reduce(graph, X: torch.Tensor, reduce: str, value=None, return_arg: boo
     g = EdgeGraph.of(graph)
     op = REDUCE_CODE[reduce]
     _, code = _backend()
-    if X.dtype not in code:
-        raise TypeError(f"spmm_reduce: unsupported element type {X.dtype}")
-    if reduce == "mean" and X.dtype not in FLOAT_TYPES:
-        raise TypeError(f"spmm_reduce: mean needs float32 or float64, got {X.dtype}")
-    if value is not None and value.dtype != X.dtype:
-        raise TypeError(f"spmm_reduce: value and X must have one dtype, got {value.dtype} and {X.dtype}")
+    half = X.dtype in HALF_TYPES
+    if X.dtype not in code and not (half and reduce == "mean"):
+        raise TypeError(f"spmm_reduce: unsupported element type {X.dtype}" + (" for max / min (16-bit features: mean only)" if half else ""))
+    if reduce == "mean" and X.dtype not in FLOAT_TYPES and not half:
+        raise TypeError(f"spmm_reduce: mean needs float32, float64, bfloat16 or float16, got {X.dtype}")
+    if value is not None and value.dtype != X.dtype and not (half and value.dtype == torch.float32):
+        raise TypeError(f"spmm_reduce: value and X must have one dtype (float32 values are fine beside 16-bit X), got {value.dtype} and {X.dtype}")
     if X.dim() != 2 or X.size(0) != g.ncols or X.size(1) < 1:
         raise ValueError(f"spmm_reduce: X must be [{g.ncols}, h], got {tuple(X.shape)}")
     if value is not None and (value.dim() != 1 or value.size(0) != g.nnz):
@@ -139,7 +147,7 @@ def spmm_reduce(graph, X: torch.Tensor, reduce: str, value=None, return_arg: boo
         raise NotImplementedError("spmm_reduce: the gradient of max / min with respect to value is not implemented (detach value)")
     home = X.device
     Xd = X.to(g.device).contiguous()
-    vd = None if value is None else value.to(g.device).contiguous()
+    vd = None if value is None else value.to(g.device, _compute_dtype(X.dtype)).contiguous()
     if reduce == "mean":
         return SpmmMean.apply(g, vd, Xd).to(home)
     out, arg = SpmmArgReduce.apply(g, vd, Xd, op, bool(return_arg))
@@ -148,9 +156,9 @@ def spmm_reduce(graph, X: torch.Tensor, reduce: str, value=None, return_arg: boo
 
 def matmul_reduce(adj, B: torch.Tensor, reduce: str):
     """``torch_sparse.matmul(adj, B, reduce)`` for mean / max / min on the device: adj a SparseTensor or a ``backend_pim`` wrapper;
-    its stored values (cast to B's dtype) weigh the entries when it has them, unit weights otherwise"""
+    its stored values (cast to B's dtype; to float32 beside 16-bit B) weigh the entries when it has them, unit weights otherwise"""
     raw = adj.raw if hasattr(adj, "raw") and hasattr(adj.raw, "csr") else adj
     value = raw.storage.value() if hasattr(raw, "storage") else None
     if value is not None:
-        value = (value if reduce == "mean" else value.detach()).to(B.dtype)
+        value = (value if reduce == "mean" else value.detach()).to(_compute_dtype(B.dtype) if reduce == "mean" else B.dtype)
     return spmm_reduce(EdgeGraph.of(adj), B, reduce, value=value)

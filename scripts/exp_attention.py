@@ -11,9 +11,13 @@ warm-up.  JSON lines:
     (a) gat_aggregate forward; (b) the unfused sequence of GATConv for the same inputs -- score composite + edge_softmax +
     spmm_values -- and each part on its own; (c) spmm_values heads = 8 alone, the floor of the gather; (d) forward + backward of
     both paths with torch.cuda.max_memory_allocated for each.
-    python scripts/exp_attention.py [--iters 10] [--section all|base|fused] [--forward-only]
+  16-bit features (--section half, on its own: profiles/exp_half.txt), per storage type of X (FLT32, BF16, FLT16; values, node terms
+    and sums float32 throughout), two rounds: spmm_values heads = 1 and 8, gat_aggregate heads = 8, spmm_reduce mean and sddmm (time,
+    gather rate: every stored entry reads one X row of h * 4 or h * 2 bytes); then forward + backward of a fused GATConv layer
+    (h -> 8 heads of h / 8) in FLT32 and BF16.  --dtypes f32 restricts it to calls that exist without the 16-bit codes.
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half] [--forward-only] [--dtypes f32,bf16,f16]
   --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
-  (profiles/exp_gat_fused.txt)."""
+  (profiles/exp_gat_fused.txt); all = base + fused."""
 import argparse
 import json
 import os
@@ -112,6 +116,58 @@ def fused_section(g, x, n, nnz, h, iters, dev, line, backward=True):
          unfused_peak_above_start_gb=round((res["unfused"][2] - res["unfused"][1]) / 1e9, 2), nnz_heads_tensor_gb=round(nnz * heads * 4 / 1e9, 2))
 
 
+HALF_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+
+
+def half_section(g, n, nnz, h, iters, dev, line, names):
+    """the gather family per storage type of X, then a fused GAT layer forward + backward"""
+    from pygim_amd import gnn, reduce
+
+    heads, slope = 8, 0.2
+    gen = torch.Generator(device=dev).manual_seed(3)
+    v1 = torch.rand(nnz, 1, device=dev, generator=gen)
+    v8 = torch.rand(nnz, heads, device=dev, generator=gen)
+    a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+    a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+    x32 = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform")
+    g32 = synth.features(n, h, torch.float32, seed=1, device=dev, kind="uniform")
+    for name in names:
+        dt = HALF_DTYPES[name]
+        x, gr = x32.to(dt), g32.to(dt)
+        gathered = nnz * h * x.element_size()
+        for rnd in range(2):
+            t1 = timed(lambda: attention._run_spmm_values(g, v1, x, 1), iters)
+            t8 = timed(lambda: attention._run_spmm_values(g, v8, x, heads), iters)
+            tg = timed(lambda: attention._run_gat_aggregate(g, a_dst, a_src, x, heads, slope, False), iters)
+            tm = timed(lambda: reduce._run_spmm_reduce(g, None, x, reduce.REDUCE_CODE["mean"], False), iters)
+            sd = timed(lambda: autograd.sddmm(g.rowptr, g.col, gr, x), iters)
+            ms = dict(spmm_values_heads1=t1, spmm_values_heads8=t8, gat_aggregate_heads8=tg, mean=tm, sddmm=sd)
+            line(what="16-bit features: the gather family", x_dtype=name, round=rnd, bytes_per_x_row=h * x.element_size(),
+                 **{k + "_ms": round(v, 3) for k, v in ms.items()}, **{k + "_gather_tb_s": round(gathered / v / 1e9, 2) for k, v in ms.items()})
+        del x, gr
+    del v1, v8, a_dst, a_src, g32
+    g.transposed()
+    for name in [k for k in names if k in ("f32", "bf16")]:
+        dt = HALF_DTYPES[name]
+        torch.manual_seed(0)
+        conv = gnn.GATConv(h, h // heads, heads=heads, fused=True).to(dev, dt)
+        x = x32.to(dt)
+
+        def step():
+            conv.zero_grad(set_to_none=True)
+            conv(x, g).float().square().mean().backward()
+
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ms = [timed(step, max(2, iters // 3)) for _ in range(2)]
+        line(what="fused GATConv forward + backward, heads=8", x_dtype=name, ms_round0=round(ms[0], 2), ms_round1=round(ms[1], 2),
+             peak_above_start_gb=round((torch.cuda.max_memory_allocated() - base) / 1e9, 2))
+        del conv, x
+
+
 def base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line):
     """spmm_values, edge_softmax, the workspaces, new values through a new group: the record in profiles/exp_attention.txt"""
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -198,7 +254,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="all", choices=["all", "base", "fused"])
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half"])
+    ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half: the storage types of X to measure")
     ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -217,6 +274,9 @@ def main():
         base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line)
     if args.section in ("all", "fused"):   # after the recorded parts, which keep the allocator and cache state they were taken under
         fused_section(g, x, n, nnz, h, iters, dev, line, backward=not args.forward_only)
+    if args.section == "half":
+        del x
+        half_section(g, n, nnz, h, iters, dev, line, args.dtypes.split(","))
     torch.ops.pim_ops.dpu_release()
 
 
