@@ -61,7 +61,7 @@ typedef enum {
     PYGIM_FLT32 = 4,
     PYGIM_DBL64 = 5,
     /* 16-bit FEATURE types (IEEE binary16, bfloat16).  Valid only for pygim_sddmm, pygim_spmm_values, pygim_gat_aggregate,
-     * pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
+     * pygim_sparse_attention, pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
      * point -- group creation, edge softmax, the max / min reductions and their backward, the quantisers -- rejects them like
      * an unknown type. */
     PYGIM_FLT16 = 6,
@@ -73,7 +73,8 @@ typedef enum {
  *   pygim_sddmm          G, X 16-bit;      out [nnz] float32 (nothing is rounded)
  *   pygim_spmm_values    X, out 16-bit;    values float32
  *   pygim_gat_aggregate  X, out 16-bit;    a_dst, a_src, lse float32
- *   pygim_spmm_reduce    X, out 16-bit;    values float32 or NULL; PYGIM_REDUCE_MEAN only (MAX / MIN: PYGIM_ERR_INVALID)
+ *   pygim_sparse_attention  Q, K, V, out 16-bit;  products, scores and lse float32
+ *   pygim_spmm_reduce   X, out 16-bit;    values float32 or NULL; PYGIM_REDUCE_MEAN only (MAX / MIN: PYGIM_ERR_INVALID)
  * Strides (ldx, ldo, ldg) count 16-bit elements.  An element of X is widened to float32 as it is read (exact) and the arithmetic is
  * the FLT32 arithmetic of the call: accumulators, the exchange between lane groups, the workspace slots of rows cut across waves and
  * the kernels that join them, the online-softmax state (m, l, acc), the mean's division and lse are float32 -- so the *_workspace
@@ -82,6 +83,7 @@ typedef enum {
  * Bounds, with u = 2^-11 (FLT16) / 2^-8 (BF16), the half-ulp of that one rounding, and `exact` the exact result on the 16-bit inputs:
  *   spmm_values, mean     |out - exact| <= u |exact| + the FLT32 bound of the call (1e-5 sum |value . x|; the mean's divided by the count)
  *   gat_aggregate         |out - exact| <= u |exact| + 2e-5 sum_e p[e] |x[e]|;  lse as for FLT32
+ *   sparse_attention      |out - exact| <= u |exact| + the FLT32 bound of the call;  lse as for FLT32
  *   sddmm                 the FLT32 bound (1e-5 sum_f |G . X|)
  * 16-byte gathers need (h / heads) % 8 == 0, strides that are multiples of 8 elements and 16-byte aligned X / G / out; otherwise a
  * lane reads one element.  No atomics and fixed orders as for FLT32: the same bits on every launch. */
@@ -278,6 +280,31 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
                         const void *a_dst /* [nrows, heads] */, const void *a_src /* [ncols, heads] */, int64_t heads,
                         double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo,
                         void *lse /* [nrows, heads] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+/*   pygim_sparse_attention:  scaled dot-product attention over the stored entries (TransformerConv, graph transformers) in one pass
+ *     -- scores, softmax and product, with nothing of size nnz read (besides colind) or written:
+ *       s[e, k]   = scale * sum_{f in head k} Q[r, f] * K[colind[e], f]      e over the entries of row r, hd = h / heads, k = f / hd
+ *       out[r, f] = sum_e exp(s[e, k] - m[r, k]) * V[colind[e], f] / l[r, k],   m = max_e s,  l = sum_e exp(s - m)
+ *       lse[r, k] = m[r, k] + log(l[r, k])        when lse is not NULL ([nrows, heads] contiguous)
+ *     The contract of pygim_gat_aggregate: FLT32 and DBL64 (FLT16 / BF16: Q, K, V and out 16-bit, lse float32), device pointers only,
+ *     a valid CSR guaranteed by the caller, nnz = 0 and empty rows allowed (out = 0, lse = 0), heads >= 1 divides h, Q: [nrows, h],
+ *     K and V: [max column + 1, h], row strides ldq, ldk, ldv, ldo >= h, work is only enqueued on `stream`, scratch from the caller
+ *     (pygim_sparse_attention_workspace bytes, 16-byte aligned), no atomics, the same bits on every launch, out has the same bits
+ *     with and without lse.  A head is at most 256 features wide (h / heads <= 256; any heads >= 1): wider heads are rejected.  The
+ *     dot product of an entry is a fixed-order sum (a lane's features in ascending order, then an xor butterfly over the head's
+ *     lanes); the softmax is the online one of pygim_gat_aggregate, stable for finite scores of any magnitude.
+ *     Bounds, with EPS = 1e-5 (FLT32, FLT16, BF16) / 1e-12 (DBL64), p the exact probabilities and
+ *     Delta[r, k] = EPS * |scale| * max_e sum_{f in head k} |Q[r, f] * K[colind[e], f]|   (the pygim_sddmm bound on a score):
+ *       |out - exact| <= (2 EPS + 2 Delta[r, k]) * sum_e p[e] * |v[e]|     (a score error of Delta moves a probability by at most
+ *                                                                           e^(2 Delta) - 1)
+ *       |lse - exact| <= 2 EPS * (1 + |exact|) + Delta[r, k]
+ *     and for FLT16 / BF16 the one rounding of out added: u |exact|, u = 2^-11 / 2^-8, exact on the 16-bit inputs.
+ *     PYGIM_ERR_INVALID (-1 from the workspace function): an integer type, heads not dividing h, h / heads > 256, a workspace too
+ *     small or misaligned.                                                                                                          */
+int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
+int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                           const void *Q, int64_t ldq, const void *K, int64_t ldk, const void *V, int64_t ldv,
+                           int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
+                           void *lse /* [nrows, heads] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
  *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1

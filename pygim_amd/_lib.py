@@ -22,13 +22,13 @@ EXPORTS = [
     "pygim_group_lds_tiles", "pygim_group_lds_runs", "pygim_group_serial", "pygim_group_host_windows",
     "pygim_group_create_transposed", "pygim_sddmm",
     "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
-    "pygim_gat_aggregate", "pygim_gat_aggregate_workspace",
+    "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
 INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
-FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate and spmm_reduce mean only (include/pygim_hip.h)
+FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
 
@@ -76,6 +76,10 @@ def lib():
         L.pygim_gat_aggregate.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, ctypes.c_double, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_gat_aggregate_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
         L.pygim_gat_aggregate_workspace.restype = c_i64
+        L.pygim_sparse_attention.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, c_i64, ctypes.c_double, vp, c_i64, vp, vp,
+                                             c_i64, vp]
+        L.pygim_sparse_attention_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
+        L.pygim_sparse_attention_workspace.restype = c_i64
         L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
@@ -248,6 +252,24 @@ def gat_aggregate(dtype, nrows, rowptr_ptr, col_ptr, nnz, a_dst_ptr, a_src_ptr, 
     check(lib().pygim_gat_aggregate(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(a_dst_ptr), _vp(a_src_ptr), int(heads),
                                     float(negative_slope), _vp(x_ptr), int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr),
                                     int(ws_bytes), _vp(stream)))
+
+
+def sparse_attention_workspace(dtype, nrows, nnz, h, heads):
+    """bytes of scratch sparse_attention needs for this shape (a function of the numbers alone; heads wider than 256 are rejected)"""
+    n = int(lib().pygim_sparse_attention_workspace(int(dtype), int(nrows), int(nnz), int(h), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad sparse_attention_workspace arguments")
+    return n
+
+
+def sparse_attention(dtype, nrows, rowptr_ptr, col_ptr, nnz, q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, h, heads, scale, out_ptr, ldo, lse_ptr, ws_ptr,
+                     ws_bytes, stream=0):
+    """out[r, f] = sum_e softmax_e(scale * Q[r, head k] . K[col[e], head k]) * V[col[e], f] over the entries of row r, k the head of f, in one
+    pass; lse_ptr (0: not wanted) receives max + log(sum exp) per row and head (device pointers; FLT32 / DBL64, or FLT16 / BF16 Q, K, V and
+    out with float32 lse; h / heads <= 256)"""
+    check(lib().pygim_sparse_attention(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(q_ptr), int(ldq), _vp(k_ptr), int(ldk),
+                                       _vp(v_ptr), int(ldv), int(h), int(heads), float(scale), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr),
+                                       int(ws_bytes), _vp(stream)))
 
 
 def spmm_reduce_workspace(dtype, op, nrows, nnz, h):

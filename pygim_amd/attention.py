@@ -1,5 +1,5 @@
-"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate`` and the
-structure they share.
+"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate`` and
+``sparse_attention``, and the structure they share.
 
 A device group (``to_pim_group``) freezes its edge values when it is created -- on the fast path they are compiled into the code
 stream -- so ``mul`` multiplies by those values for as long as the group lives.  Values that change between calls (attention
@@ -16,15 +16,19 @@ pygim_edge_softmax_backward: no atomics, the same bits on every run), differenti
   ``leaky_relu(a_dst[row] + a_src[col])``, a function of two per-node numbers, so scores, an online softmax and the product with ``X``
   run inside the gather of ``spmm_values``.  Nothing of size nnz is written by the forward or kept for the backward (it saves
   ``a_dst``, ``a_src``, ``X``, ``out`` and the per-row ``lse``); the backward recomputes the probabilities from them.
+* :func:`sparse_attention` scaled dot-product attention over the stored entries in one pass (pygim_sparse_attention): the score of an
+  entry is ``scale * Q[row] . K[col]`` per head, reduced across the lanes of a head inside the gather; the forward saves ``Q``, ``K``,
+  ``V``, ``out`` and ``lse``, the backward recomputes the probabilities and runs on ``pygim_sddmm`` and ``spmm_values``.
 
-16-bit features: ``X`` of ``spmm_values`` and ``gat_aggregate`` (and of ``spmm_reduce(..., "mean")``, ``autograd.sddmm``) may be
+16-bit features: ``X`` of ``spmm_values`` and ``gat_aggregate``, ``Q`` / ``K`` / ``V`` of ``sparse_attention`` (and of ``spmm_reduce(..., "mean")``, ``autograd.sddmm``) may be
 bfloat16 or float16 -- what ``model.to(torch.bfloat16)`` and ``torch.autocast`` hand a layer.  Only the feature matrices are stored
 in 16 bits: edge values, ``a_dst`` / ``a_src``, ``lse``, every partial sum and the softmax state are float32 (the wrappers upcast
 16-bit values and node terms), and a result row is rounded once, to nearest even, where it is stored.  ``edge_softmax`` stays float32 /
 float64.
 
 Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph, 16-bit device groups
-(``mul``), 16-bit ``edge_softmax`` and 16-bit max / min.
+(``mul``), 16-bit ``edge_softmax`` and 16-bit max / min; for ``sparse_attention`` also a fused backward kernel, edge features / ``beta``
+of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass composition).
 """
 from __future__ import annotations
 
@@ -366,4 +370,135 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
     ct = _compute_dtype(X.dtype)
     out = GatAggregate.apply(g, a_dst.to(g.device, ct).contiguous(), a_src.to(g.device, ct).contiguous(), X.to(g.device).contiguous(),
                              float(negative_slope))
+    return out.to(home)
+
+
+SA_MAX_HEAD = 256   # features of one head the fused kernel takes (include/pygim_hip.h); wider heads run as the three-pass composition
+
+
+def _head_dots(g: EdgeGraph, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
+    """[nnz, heads]: ``A[row(e), head k] . B[col[e], head k]`` for every stored entry, one ``pygim_sddmm`` per head on strided views of
+    A [nrows, h] and B [ncols, h] (contiguous, on g.device, one dtype); float32 beside 16-bit operands, else their dtype"""
+    L, _ = _backend()
+    h = A.size(1)
+    hd, es = h // heads, A.element_size()
+    per_head = torch.empty((heads, g.nnz), dtype=_compute_dtype(A.dtype), device=g.device)
+    if g.nnz > 0:
+        for k in range(heads):
+            L.sddmm(_gather_code(A.dtype), g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, A.data_ptr() + k * hd * es, A.stride(0),
+                    B.data_ptr() + k * hd * es, B.stride(0), hd, per_head[k].data_ptr(), _stream(g.device))
+    return per_head.t().contiguous()
+
+
+class HeadScores(torch.autograd.Function):
+    """``s[e, k] = scale * Q[row(e), head k] . K[col[e], head k]``: the scores of the three-pass composition"""
+
+    @staticmethod
+    def forward(ctx, g, Q, K, heads, scale):
+        ctx.g, ctx.heads, ctx.scale = g, heads, scale
+        ctx.save_for_backward(Q, K)
+        return _head_dots(g, Q, K, heads).mul_(scale)
+
+    @staticmethod
+    def backward(ctx, dS):
+        g, heads = ctx.g, ctx.heads
+        Q, K = ctx.saved_tensors
+        dS = dS * ctx.scale
+        dQ = _run_spmm_values(g, dS, K, heads) if ctx.needs_input_grad[1] else None
+        dK = None
+        if ctx.needs_input_grad[2]:
+            gt, perm = g.transposed()
+            dK = _run_spmm_values(gt, dS.index_select(0, perm), Q, heads)
+        return None, dQ, dK, None, None
+
+
+def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_lse: bool):
+    """Q [nrows, h], K and V [ncols, h] contiguous on g.device, one dtype -> (out [nrows, h] in that dtype, lse [nrows, heads] in the
+    compute dtype or None)"""
+    L, _ = _backend()
+    dt = _gather_code(Q.dtype)
+    h = Q.size(1)
+    out = torch.empty((g.nrows, h), dtype=Q.dtype, device=g.device)
+    lse = torch.empty((g.nrows, heads), dtype=_compute_dtype(Q.dtype), device=g.device) if want_lse else None
+    if g.nrows == 0:
+        return out, lse
+    ws = _workspace(L.sparse_attention_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
+    L.sparse_attention(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0),
+                       V.data_ptr(), V.stride(0), h, heads, scale, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
+                       _stream(g.device))
+    return out, lse
+
+
+class SparseAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, Q, K, V, heads, scale):
+        need = any(ctx.needs_input_grad[1:4])
+        out, lse = _run_sparse_attention(g, Q, K, V, heads, scale, need)
+        if need:
+            ctx.g, ctx.heads, ctx.scale = g, heads, scale
+            ctx.save_for_backward(Q, K, V, out, lse)   # node-sized, all of them
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        g, heads, scale = ctx.g, ctx.heads, ctx.scale
+        Q, K, V, out, lse = ctx.saved_tensors
+        G = G.contiguous()
+        hd = Q.size(1) // heads
+        row = g.row.long()
+        gt, perm = g.transposed()
+        # the probabilities again, from the scores and the row's log-sum-exp: [nnz, heads], transient, in the compute dtype
+        p = _head_dots(g, Q, K, heads).mul_(scale).sub_(lse.index_select(0, row)).exp_()
+        dV = _run_spmm_values(gt, p.index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
+        dQ = dK = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ds = _head_dots(g, G, V, heads)   # dP
+            if Q.dtype in HALF_TYPES:
+                # out was rounded to 16 bits when it was stored (GatAggregate.backward): sum_e p * dp itself, as a float32 row sum per head
+                delta = _run_spmm_values(g, p * ds, torch.ones((g.ncols, heads), dtype=p.dtype, device=g.device), heads)
+            else:
+                delta = (G * out).view(g.nrows, heads, hd).sum(-1)   # = sum_e p * dp per (row, head), without a pass over the entries
+            ds.sub_(delta.index_select(0, row)).mul_(p).mul_(scale)   # dS = scale * P * (dP - delta[row])
+            del p
+            if ctx.needs_input_grad[1]:
+                dQ = _run_spmm_values(g, ds, K, heads)
+            if ctx.needs_input_grad[2]:
+                dK = _run_spmm_values(gt, ds.index_select(0, perm), Q, heads)
+        return None, dQ, dK, dV, None, None
+
+
+def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int = 1, scale=None, fused: bool = True) -> torch.Tensor:
+    """scaled dot-product attention over the stored entries: with ``hd = h // heads``, ``k = f // hd`` and e over the entries of row r
+
+    ``out[r, f] = sum_e softmax_e(scale * Q[r, head k] . K[col[e], head k]) * V[col[e], f]``
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; Q [rows, h], K and V [columns, h] with ``h % heads == 0``; all
+    float32, all float64, or all three the same 16-bit type (products, scores, softmax state and sums are then float32 and ``out`` is
+    rounded once per element).  ``scale`` defaults to ``1 / sqrt(h // heads)``.  Empty rows give 0; duplicates are separate entries.
+    ``fused=True``: one kernel, one pass over the entries (pygim_sparse_attention), nothing of size nnz written or saved -- the
+    backward recomputes the probabilities from ``Q``, ``K`` and the per-row ``lse`` and runs on ``pygim_sddmm`` and ``spmm_values``
+    (deterministic; its ``[nnz, heads]`` tensors are transient).  ``fused=False``: the three-pass composition -- per-head sddmm scores,
+    ``edge_softmax``, ``spmm_values`` -- which heads wider than 256 features take in either case.  Differentiable in Q, K and V, each
+    gradient in its operand's dtype; no double backward.  Runs on the device; CPU tensors are staged there and the result comes back
+    to Q's device."""
+    g = EdgeGraph.of(graph)
+    heads = int(heads)
+    if Q.dtype not in FLOAT_TYPES + HALF_TYPES or K.dtype != Q.dtype or V.dtype != Q.dtype:
+        raise TypeError(f"sparse_attention: Q, K and V must all be float32, float64, bfloat16 or float16, got {Q.dtype}, {K.dtype} and {V.dtype}")
+    if Q.dim() != 2 or Q.size(0) != g.nrows:
+        raise ValueError(f"sparse_attention: Q must be [{g.nrows}, h], got {tuple(Q.shape)}")
+    h = Q.size(1)
+    if K.dim() != 2 or V.dim() != 2 or tuple(K.shape) != (g.ncols, h) or tuple(V.shape) != (g.ncols, h):
+        raise ValueError(f"sparse_attention: K and V must be [{g.ncols}, {h}], got {tuple(K.shape)} and {tuple(V.shape)}")
+    if heads < 1 or h < 1 or h % heads != 0:
+        raise ValueError(f"sparse_attention: heads = {heads} must divide h = {h}")
+    hd = h // heads
+    scale = hd ** -0.5 if scale is None else float(scale)
+    home = Q.device
+    q, k, v = (t.to(g.device).contiguous() for t in (Q, K, V))
+    if fused and hd <= SA_MAX_HEAD:
+        out = SparseAttention.apply(g, q, k, v, heads, scale)
+    else:
+        p = EdgeSoftmax.apply(g, HeadScores.apply(g, q, k, heads, scale), heads)
+        out = SpmmValues.apply(g, p, v, heads)
     return out.to(home)

@@ -26,6 +26,7 @@
 #include "row_gather_dev.hpp"
 #include "edge_softmax_dev.hpp"
 #include "gat_aggregate_dev.hpp"
+#include "sparse_attention_dev.hpp"
 #include "spmm_reduce_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -727,6 +728,35 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
         launch_gat_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
                                    (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace,
                                    (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
+    (void)nrows;
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0 || h / heads > (int64_t)SA_MAX_HEAD) return -1;
+    return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
+}
+
+int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq, const void *K,
+                           int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo, void *lse,
+                           void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "sparse_attention: type must be FLT32, DBL64, FLT16 or BF16");
+    if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "sparse_attention: heads must divide h");
+    if (h >= 1 && h / heads > (int64_t)SA_MAX_HEAD) return fail(PYGIM_ERR_INVALID, "sparse_attention: a head is at most 256 features wide");
+    if (int rc = check_csr_call("sparse_attention", "rowptr / colind / Q / K / V / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldq < ldk ? ldq : ldk,
+                                ldv < ldo ? ldv : ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {Q, nnz > 0}, {K, nnz > 0}, {V, nnz > 0}},
+                                pygim_sparse_attention_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
+        return rc;
+    with_gather_types(dtype, [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        launch_sparse_attention<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
+                                      (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
+                                      (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;

@@ -17,12 +17,19 @@ is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values froze
 bfloat16 / float16 features after ``model.to(torch.bfloat16)`` or under ``torch.autocast`` (so is ``SAGEConv(aggr="mean")``).
 ``GATConv(..., fused=True)`` / ``GAT(..., fused=True)`` aggregate with ``gat_aggregate`` instead: scores, softmax and product in one
 kernel, no ``[nnz, heads]`` tensor written or kept for the backward.  The default (``fused=False``) is the layer as before.
+
+TransformerConv / GraphTransformer are the dot-product attention layer (PyG's TransformerConv without edge features or ``beta``) on
+``pygim_amd.attention.sparse_attention``: one kernel per layer when ``fused`` is set, the three-pass composition otherwise; the same
+dtypes as GATConv.
 """
 import torch
 import torch.nn.functional as F
 from torch.nn import BatchNorm1d, Linear, ReLU, Sequential
 
 from .quantize import message_and_aggregate
+
+
+TRANSFORMER_FUSED_DEFAULT = True   # the fused forward beat the composition in both rounds of profiles/exp_sparse_attention.txt
 
 
 class GCNConv(torch.nn.Module):
@@ -108,6 +115,32 @@ class GATConv(torch.nn.Module):
         return out if self.bias is None else out + self.bias
 
 
+class TransformerConv(torch.nn.Module):
+    """PyG's TransformerConv arithmetic without edge features or ``beta``, on the adjacency as given: q = lin_query(x), k = lin_key(x),
+    v = lin_value(x) as [N, H, F];  score of stored entry (i, j) = q[i] . k[j] / sqrt(F) per head;  p = softmax of the scores over the
+    entries of row i;  out[i] = sum_j p[(i, j)] * v[j] per head; heads concatenated or averaged;  + lin_skip(x) with ``root_weight``.
+    ``fused=True``: scores, softmax and product are one ``sparse_attention`` kernel (heads wider than 256 features run unfused)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, root_weight=True, bias=True, fused=TRANSFORMER_FUSED_DEFAULT, **_):
+        super().__init__()
+        self.fused = bool(fused)
+        self.heads, self.out_channels, self.concat, self.root_weight = int(heads), int(out_channels), bool(concat), bool(root_weight)
+        width = self.heads * self.out_channels
+        self.lin_key = Linear(in_channels, width, bias=bias)
+        self.lin_query = Linear(in_channels, width, bias=bias)
+        self.lin_value = Linear(in_channels, width, bias=bias)
+        self.lin_skip = Linear(in_channels, width if self.concat else self.out_channels, bias=bias) if self.root_weight else None
+
+    def forward(self, x, adj_t):
+        from .attention import EdgeGraph, sparse_attention
+
+        g = EdgeGraph.of(adj_t)
+        out = sparse_attention(g, self.lin_query(x), self.lin_key(x), self.lin_value(x), heads=self.heads, fused=self.fused)
+        if not self.concat:
+            out = out.view(-1, self.heads, self.out_channels).mean(1)
+        return out if self.lin_skip is None else out + self.lin_skip(x)
+
+
 def folded_epilogue(conv_bias, bn):
     """bias + eval-mode BatchNorm as ONE affine map per feature: bn(y + bias) = a * y + b with
     a = weight / sqrt(running_var + eps), b = (bias - running_mean) * a + bn.bias"""
@@ -163,3 +196,10 @@ class GAT(_Stack):
         assert hidden_channels % heads == 0, "GAT: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
                          lambda h: GATConv(h, h // heads, heads=heads, concat=True, fused=fused))
+
+
+class GraphTransformer(_Stack):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=TRANSFORMER_FUSED_DEFAULT):
+        assert hidden_channels % heads == 0, "GraphTransformer: heads must divide hidden_channels (the heads are concatenated)"
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: TransformerConv(h, h // heads, heads=heads, concat=True, fused=fused))

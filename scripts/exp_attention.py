@@ -15,7 +15,11 @@ warm-up.  JSON lines:
     and sums float32 throughout), two rounds: spmm_values heads = 1 and 8, gat_aggregate heads = 8, spmm_reduce mean and sddmm (time,
     gather rate: every stored entry reads one X row of h * 4 or h * 2 bytes); then forward + backward of a fused GATConv layer
     (h -> 8 heads of h / 8) in FLT32 and BF16.  --dtypes f32 restricts it to calls that exist without the 16-bit codes.
-    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half] [--forward-only] [--dtypes f32,bf16,f16]
+  sparse dot-product attention (--section dot, on its own: profiles/exp_sparse_attention.txt), heads = 1 and 8, FLT32 and BF16 storage of
+    Q, K, V (--dtypes), two rounds: (a) sparse_attention forward without and with lse; (b) the three-pass composition -- one pygim_sddmm
+    per head, edge_softmax, spmm_values; (c) gat_aggregate at the same heads; (d) spmm_values twice, the floor of the gather (every
+    entry reads one K row and one V row); then forward + backward of both paths with torch.cuda.max_memory_allocated for each.
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot] [--forward-only] [--dtypes f32,bf16,f16]
   --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
   (profiles/exp_gat_fused.txt); all = base + fused."""
 import argparse
@@ -168,6 +172,64 @@ def half_section(g, n, nnz, h, iters, dev, line, names):
         del conv, x
 
 
+def dot_section(g, n, nnz, h, iters, dev, line, names, backward=True):
+    """the fused dot-product attention next to the three passes it replaces, to gat_aggregate and to two plain gathers"""
+    g.transposed()   # built once per graph, before any backward is measured
+    q32, k32, v32, g32 = (synth.features(n, h, torch.float32, seed=sd, device=dev, kind="uniform") for sd in (5, 6, 7, 8))
+    for name in names:
+        dt = HALF_DTYPES[name]
+        Q, K, V, G = (t.to(dt) for t in (q32, k32, v32, g32))
+        for heads in (1, 8):
+            scale = (h // heads) ** -0.5
+            gen = torch.Generator(device=dev).manual_seed(4)
+            a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+            a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+
+            def composition():
+                sc = attention._head_dots(g, Q, K, heads).mul_(scale)
+                return attention._run_spmm_values(g, attention._run_edge_softmax(g, sc, None, heads), V, heads)
+
+            P = attention._run_edge_softmax(g, attention._head_dots(g, Q, K, heads).mul_(scale), None, heads)
+            got = attention._run_sparse_attention(g, Q, K, V, heads, scale, False)[0]
+            tol = dict(rtol=1e-4, atol=1e-5) if dt == torch.float32 else dict(rtol=2e-2, atol=1e-3)
+            agree = bool(torch.allclose(got.float(), attention._run_spmm_values(g, P, V, heads).float(), **tol))
+            del got
+            for rnd in range(2):
+                ta = timed(lambda: attention._run_sparse_attention(g, Q, K, V, heads, scale, False), iters)
+                tl = timed(lambda: attention._run_sparse_attention(g, Q, K, V, heads, scale, True), iters)
+                tb = timed(composition, iters)
+                tg = timed(lambda: attention._run_gat_aggregate(g, a_dst, a_src, V, heads, 0.2, False), iters)
+                t2 = timed(lambda: (attention._run_spmm_values(g, P, K, heads), attention._run_spmm_values(g, P, V, heads)), iters)
+                line(what="sparse_attention fused vs composition forward", x_dtype=name, heads=heads, round=rnd, a_sparse_attention_ms=round(ta, 3),
+                     a_with_lse_ms=round(tl, 3), b_composition_ms=round(tb, 3), c_gat_aggregate_ms=round(tg, 3), d_two_spmm_values_ms=round(t2, 3),
+                     a_over_b=round(ta / tb, 4), a_over_c=round(ta / tg, 4), a_over_d=round(ta / t2, 4),
+                     gather_tb_s=round(2 * nnz * h * Q.element_size() / ta / 1e9, 2), same_result=agree)
+            del P
+            if not backward:
+                continue
+            leaves = [t.clone().requires_grad_() for t in (Q, K, V)]
+            res = {}
+            for path, fused in (("fused", True), ("unfused", False)):
+                def step():
+                    for t in leaves:
+                        t.grad = None
+                    attention.sparse_attention(g, *leaves, heads=heads, fused=fused).backward(G)
+
+                step()
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                ms = timed(step, max(2, iters // 3))
+                res[path] = (ms, base, torch.cuda.max_memory_allocated())
+            del leaves
+            line(what="sparse_attention forward + backward", x_dtype=name, heads=heads, fused_ms=round(res["fused"][0], 2),
+                 unfused_ms=round(res["unfused"][0], 2), fused_peak_above_start_gb=round((res["fused"][2] - res["fused"][1]) / 1e9, 2),
+                 unfused_peak_above_start_gb=round((res["unfused"][2] - res["unfused"][1]) / 1e9, 2), nnz_heads_tensor_gb=round(nnz * heads * 4 / 1e9, 2))
+        del Q, K, V, G
+    line(what="sparse_attention workspace bytes", heads8=_lib.sparse_attention_workspace(_lib.FLT32, n, nnz, h, 8))
+
+
 def base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line):
     """spmm_values, edge_softmax, the workspaces, new values through a new group: the record in profiles/exp_attention.txt"""
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -254,8 +316,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half"])
-    ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half: the storage types of X to measure")
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot"])
+    ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half / dot: the storage types of the features to measure")
     ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -277,6 +339,9 @@ def main():
     if args.section == "half":
         del x
         half_section(g, n, nnz, h, iters, dev, line, args.dtypes.split(","))
+    if args.section == "dot":
+        del x
+        dot_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")], backward=not args.forward_only)
     torch.ops.pim_ops.dpu_release()
 
 
