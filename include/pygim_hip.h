@@ -61,7 +61,7 @@ typedef enum {
     PYGIM_FLT32 = 4,
     PYGIM_DBL64 = 5,
     /* 16-bit FEATURE types (IEEE binary16, bfloat16).  Valid only for pygim_sddmm, pygim_spmm_values, pygim_gat_aggregate,
-     * pygim_sparse_attention, pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
+     * pygim_sparse_attention, pygim_gatv2_aggregate, pygim_gatv2_backward, pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
      * point -- group creation, edge softmax, the max / min reductions and their backward, the quantisers -- rejects them like
      * an unknown type. */
     PYGIM_FLT16 = 6,
@@ -74,6 +74,8 @@ typedef enum {
  *   pygim_spmm_values    X, out 16-bit;    values float32
  *   pygim_gat_aggregate  X, out 16-bit;    a_dst, a_src, lse float32
  *   pygim_sparse_attention  Q, K, V, out 16-bit;  products, scores and lse float32
+ *   pygim_gatv2_aggregate   x_dst, x_src, out 16-bit;  att, z, scores and lse float32
+ *   pygim_gatv2_backward    x_own, x_oth, G, d_own 16-bit;  att, lse, delta, datt float32
  *   pygim_spmm_reduce   X, out 16-bit;    values float32 or NULL; PYGIM_REDUCE_MEAN only (MAX / MIN: PYGIM_ERR_INVALID)
  * Strides (ldx, ldo, ldg) count 16-bit elements.  An element of X is widened to float32 as it is read (exact) and the arithmetic is
  * the FLT32 arithmetic of the call: accumulators, the exchange between lane groups, the workspace slots of rows cut across waves and
@@ -83,7 +85,7 @@ typedef enum {
  * Bounds, with u = 2^-11 (FLT16) / 2^-8 (BF16), the half-ulp of that one rounding, and `exact` the exact result on the 16-bit inputs:
  *   spmm_values, mean     |out - exact| <= u |exact| + the FLT32 bound of the call (1e-5 sum |value . x|; the mean's divided by the count)
  *   gat_aggregate         |out - exact| <= u |exact| + 2e-5 sum_e p[e] |x[e]|;  lse as for FLT32
- *   sparse_attention      |out - exact| <= u |exact| + the FLT32 bound of the call;  lse as for FLT32
+ *   sparse_attention, gatv2_aggregate   |out - exact| <= u |exact| + the FLT32 bound of the call;  lse as for FLT32
  *   sddmm                 the FLT32 bound (1e-5 sum_f |G . X|)
  * 16-byte gathers need (h / heads) % 8 == 0, strides that are multiples of 8 elements and 16-byte aligned X / G / out; otherwise a
  * lane reads one element.  No atomics and fixed orders as for FLT32: the same bits on every launch. */
@@ -305,6 +307,54 @@ int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, cons
                            const void *Q, int64_t ldq, const void *K, int64_t ldk, const void *V, int64_t ldv,
                            int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
                            void *lse /* [nrows, heads] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+/*   pygim_gatv2_aggregate:  the aggregation of a GATv2 layer (Brody et al.; PyG's GATv2Conv) in one pass -- scores, softmax and
+ *     product, with nothing of size nnz read (besides colind) or written:
+ *       z[e, f]   = x_dst[r, f] + x_src[colind[e], f]                   e over the entries of row r, hd = h / heads, k = f / hd
+ *       s[e, k]   = sum_{f in head k} att[f] * lrelu(z[e, f])           lrelu(z) = z > 0 ? z : negative_slope * z
+ *       out[r, f] = sum_e exp(s[e, k] - m[r, k]) * x_src[colind[e], f] / l[r, k],   m = max_e s,  l = sum_e exp(s - m)
+ *       lse[r, k] = m[r, k] + log(l[r, k])        when lse is not NULL ([nrows, heads] contiguous)
+ *     The contract of pygim_sparse_attention: FLT32 and DBL64 (FLT16 / BF16: x_dst, x_src and out 16-bit; att, z, the scores and lse
+ *     float32), device pointers only, a valid CSR guaranteed by the caller, nnz = 0 and empty rows allowed (out = 0, lse = 0),
+ *     heads >= 1 divides h, x_dst: [nrows, h], x_src: [max column + 1, h], att: [h] contiguous, row strides ld_dst, ld_src, ldo >= h,
+ *     work is only enqueued on `stream`, scratch from the caller (pygim_gatv2_aggregate_workspace bytes, 16-byte aligned), no
+ *     atomics, the same bits on every launch, out has the same bits with and without lse.  A head is at most 256 features wide
+ *     (h / heads <= 256): wider heads are rejected.  One gathered row per entry serves the score and the product.  A score is a
+ *     fixed-order sum (a lane's features in ascending order, then an xor butterfly over the head's lanes); the softmax is the online
+ *     one of pygim_gat_aggregate.  Bounds: those of pygim_sparse_attention with
+ *       Delta[r, k] = EPS * max_e sum_{f in head k} |att[f] * lrelu(z[e, f])|,   EPS = 1e-5 (FLT32, FLT16, BF16) / 1e-12 (DBL64):
+ *       |out - exact| <= (2 EPS + 2 Delta[r, k]) * sum_e p[e] * |x_src[e]|       |lse - exact| <= 2 EPS * (1 + |exact|) + Delta[r, k]
+ *     and for FLT16 / BF16 the one rounding of out added: u |exact|, u = 2^-11 / 2^-8, exact on the 16-bit inputs.
+ *     PYGIM_ERR_INVALID (-1 from the workspace function): an integer type, heads not dividing h, h / heads > 256, a workspace too
+ *     small or misaligned.
+ *   pygim_gatv2_backward:  one direction of its backward, a gather over "own row i, gathered row j" of the CSR it is given, with
+ *     z = x_own[i] + x_oth[j]; the probabilities are recomputed from lse, nothing of size nnz is read or written.  With G = dout
+ *     ([rows of A, h], row stride ldg), lse as the forward stored it and delta[r, k] = sum_{f in head k} G[r, f] * out[r, f] (both
+ *     [rows of A, heads] contiguous, computed by the caller; for FLT16 / BF16 float32, delta from the stored, once-rounded out as
+ *     FlashAttention's backward takes it):
+ *       p = exp(s - lse[r, k])     dp = sum_{f in head k} G[r, f] * x_src[c, f]     ds = p * (dp - delta[r, k])
+ *       t[e, f] = ds * att[f] * lrelu'(z[e, f])          lrelu'(z) = z > 0 ? 1 : negative_slope  (z == 0 takes the slope, as torch does)
+ *     transposed = 0, on the CSR of A (nrows = rows of A): x_own = x_dst, x_oth = x_src; G, lse, delta belong to the own row;
+ *       d_own[r, f] = dx_dst = sum_{e in row r} t[e, f];   datt[f] = sum_e ds * lrelu(z[e, f])   ([h] contiguous; NULL: not computed)
+ *     transposed = 1, on the CSR of A^T (nrows = columns of A, colind = the A-row of every entry; no permutation is needed): x_own =
+ *       x_src, x_oth = x_dst; G, lse, delta belong to the gathered row;  d_own[c, f] = dx_src = sum_{e with col = c} (p * G[r, f] + t[e, f]);
+ *       datt must be NULL.
+ *     d_own[0:nrows, 0:h] (row stride ldd >= h) is overwritten, rows without entries with zeros; nnz = 0 stores zeros, datt included.
+ *     Types, pointers, strides, the head cap and the stream as for pygim_gatv2_aggregate (FLT16 / BF16: x_own, x_oth, G and d_own
+ *     16-bit, each row of d_own rounded once; att, lse, delta, datt and every sum float32).  Row sums are fixed-order sums, rows cut
+ *     across waves meet in the workspace in wave order; datt is summed per wave, then level by level in a fixed order: no atomics,
+ *     the same bits on every launch.  pygim_gatv2_backward_workspace serves both directions.  PYGIM_ERR_INVALID: as for
+ *     pygim_gatv2_aggregate, and datt non-NULL with transposed.                                                                      */
+int64_t pygim_gatv2_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
+int pygim_gatv2_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                          const void *x_dst, int64_t ld_dst, const void *x_src, int64_t ld_src, const void *att /* [h] */,
+                          int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo,
+                          void *lse /* [nrows, heads] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t pygim_gatv2_backward_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
+int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                         const void *x_own, int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att /* [h] */,
+                         int64_t h, int64_t heads, double negative_slope, const void *G, int64_t ldg, const void *lse,
+                         const void *delta, void *d_own, int64_t ldd, void *datt /* [h]; NULL when transposed */,
+                         void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
  *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1

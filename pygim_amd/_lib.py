@@ -23,12 +23,13 @@ EXPORTS = [
     "pygim_group_create_transposed", "pygim_sddmm",
     "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
     "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
+    "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
 INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
-FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention and spmm_reduce mean only (include/pygim_hip.h)
+FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention, gatv2_* and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
 
@@ -80,6 +81,13 @@ def lib():
                                              c_i64, vp]
         L.pygim_sparse_attention_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
         L.pygim_sparse_attention_workspace.restype = c_i64
+        L.pygim_gatv2_aggregate.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, ctypes.c_double, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_gatv2_aggregate_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
+        L.pygim_gatv2_aggregate_workspace.restype = c_i64
+        L.pygim_gatv2_backward.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, ctypes.c_double, vp, c_i64, vp, vp, vp,
+                                           c_i64, vp, vp, c_i64, vp]
+        L.pygim_gatv2_backward_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
+        L.pygim_gatv2_backward_workspace.restype = c_i64
         L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
@@ -270,6 +278,42 @@ def sparse_attention(dtype, nrows, rowptr_ptr, col_ptr, nnz, q_ptr, ldq, k_ptr, 
     check(lib().pygim_sparse_attention(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(q_ptr), int(ldq), _vp(k_ptr), int(ldk),
                                        _vp(v_ptr), int(ldv), int(h), int(heads), float(scale), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr),
                                        int(ws_bytes), _vp(stream)))
+
+
+def gatv2_aggregate_workspace(dtype, nrows, nnz, h, heads):
+    """bytes of scratch gatv2_aggregate needs for this shape (a function of the numbers alone; heads wider than 256 are rejected)"""
+    n = int(lib().pygim_gatv2_aggregate_workspace(int(dtype), int(nrows), int(nnz), int(h), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad gatv2_aggregate_workspace arguments")
+    return n
+
+
+def gatv2_aggregate(dtype, nrows, rowptr_ptr, col_ptr, nnz, xd_ptr, ld_dst, xs_ptr, ld_src, att_ptr, h, heads, negative_slope, out_ptr, ldo, lse_ptr,
+                    ws_ptr, ws_bytes, stream=0):
+    """out[r, f] = sum_e softmax_e(sum_{f' in head k} att[f'] * leaky_relu(x_dst[r, f'] + x_src[col[e], f'])) * x_src[col[e], f] over the entries
+    of row r, k the head of f, in one pass; lse_ptr (0: not wanted) receives max + log(sum exp) per row and head (device pointers; FLT32 /
+    DBL64, or FLT16 / BF16 x_dst, x_src and out with float32 att and lse; h / heads <= 256)"""
+    check(lib().pygim_gatv2_aggregate(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(xd_ptr), int(ld_dst), _vp(xs_ptr),
+                                      int(ld_src), _vp(att_ptr), int(h), int(heads), float(negative_slope), _vp(out_ptr), int(ldo), _vp(lse_ptr),
+                                      _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def gatv2_backward_workspace(dtype, nrows, nnz, h, heads):
+    """bytes of scratch gatv2_backward needs for this shape, either direction (a function of the numbers alone)"""
+    n = int(lib().pygim_gatv2_backward_workspace(int(dtype), int(nrows), int(nnz), int(h), int(heads)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad gatv2_backward_workspace arguments")
+    return n
+
+
+def gatv2_backward(dtype, transposed, nrows, rowptr_ptr, col_ptr, nnz, own_ptr, ld_own, oth_ptr, ld_oth, att_ptr, h, heads, negative_slope, g_ptr, ldg,
+                   lse_ptr, delta_ptr, d_own_ptr, ldd, datt_ptr, ws_ptr, ws_bytes, stream=0):
+    """one direction of the backward of gatv2_aggregate on the CSR it is given: transposed = 0 (the CSR of A, own = x_dst, oth = x_src) stores
+    dx_dst into d_own and, when datt_ptr is not 0, datt [h]; transposed = 1 (the CSR of A^T, own = x_src, oth = x_dst, datt_ptr 0) stores
+    dx_src.  G, lse and delta [rows of A, heads] belong to the rows of A (device pointers; types as for gatv2_aggregate)"""
+    check(lib().pygim_gatv2_backward(int(dtype), int(transposed), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(own_ptr), int(ld_own),
+                                     _vp(oth_ptr), int(ld_oth), _vp(att_ptr), int(h), int(heads), float(negative_slope), _vp(g_ptr), int(ldg),
+                                     _vp(lse_ptr), _vp(delta_ptr), _vp(d_own_ptr), int(ldd), _vp(datt_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
 
 
 def spmm_reduce_workspace(dtype, op, nrows, nnz, h):

@@ -1,5 +1,5 @@
-"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate`` and
-``sparse_attention``, and the structure they share.
+"""Aggregation with edge values that are an operand of the call: ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate``,
+``sparse_attention`` and ``gatv2_aggregate``, and the structure they share.
 
 A device group (``to_pim_group``) freezes its edge values when it is created -- on the fast path they are compiled into the code
 stream -- so ``mul`` multiplies by those values for as long as the group lives.  Values that change between calls (attention
@@ -19,8 +19,11 @@ pygim_edge_softmax_backward: no atomics, the same bits on every run), differenti
 * :func:`sparse_attention` scaled dot-product attention over the stored entries in one pass (pygim_sparse_attention): the score of an
   entry is ``scale * Q[row] . K[col]`` per head, reduced across the lanes of a head inside the gather; the forward saves ``Q``, ``K``,
   ``V``, ``out`` and ``lse``, the backward recomputes the probabilities and runs on ``pygim_sddmm`` and ``spmm_values``.
+* :func:`gatv2_aggregate` the aggregation of a GATv2 layer in one pass (pygim_gatv2_aggregate): the score of an entry is
+  ``sum_f att[f] * leaky_relu(x_dst[row, f] + x_src[col, f])`` per head, which no composition forms without an ``[nnz, h]`` tensor; the
+  backward is fused as well (pygim_gatv2_backward, one gather on the CSR and one on the transposed CSR), nothing of size nnz is allocated.
 
-16-bit features: ``X`` of ``spmm_values`` and ``gat_aggregate``, ``Q`` / ``K`` / ``V`` of ``sparse_attention`` (and of ``spmm_reduce(..., "mean")``, ``autograd.sddmm``) may be
+16-bit features: ``X`` of ``spmm_values`` and ``gat_aggregate``, ``Q`` / ``K`` / ``V`` of ``sparse_attention``, ``x_dst`` / ``x_src`` of ``gatv2_aggregate`` (and of ``spmm_reduce(..., "mean")``, ``autograd.sddmm``) may be
 bfloat16 or float16 -- what ``model.to(torch.bfloat16)`` and ``torch.autocast`` hand a layer.  Only the feature matrices are stored
 in 16 bits: edge values, ``a_dst`` / ``a_src``, ``lse``, every partial sum and the softmax state are float32 (the wrappers upcast
 16-bit values and node terms), and a result row is rounded once, to nearest even, where it is stored.  ``edge_softmax`` stays float32 /
@@ -28,7 +31,8 @@ float64.
 
 Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph, 16-bit device groups
 (``mul``), 16-bit ``edge_softmax`` and 16-bit max / min; for ``sparse_attention`` also a fused backward kernel, edge features / ``beta``
-of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass composition).
+of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass composition); for
+``gatv2_aggregate`` edge features, ``fill_value`` / self loops, and heads wider than 256 features when fused.
 """
 from __future__ import annotations
 
@@ -501,4 +505,118 @@ def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, h
     else:
         p = EdgeSoftmax.apply(g, HeadScores.apply(g, q, k, heads, scale), heads)
         out = SpmmValues.apply(g, p, v, heads)
+    return out.to(home)
+
+
+def _run_gatv2_aggregate(g: EdgeGraph, x_dst, x_src, att, heads: int, slope: float, want_lse: bool):
+    """x_dst [nrows, h] and x_src [ncols, h] contiguous on g.device, one dtype; att [h] in the compute dtype -> (out [nrows, h] in the
+    feature dtype, lse [nrows, heads] in the compute dtype or None)"""
+    L, _ = _backend()
+    dt = _gather_code(x_src.dtype)
+    h = x_src.size(1)
+    out = torch.empty((g.nrows, h), dtype=x_src.dtype, device=g.device)
+    lse = torch.empty((g.nrows, heads), dtype=att.dtype, device=g.device) if want_lse else None
+    if g.nrows == 0:
+        return out, lse
+    ws = _workspace(L.gatv2_aggregate_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
+    L.gatv2_aggregate(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, x_dst.data_ptr(), x_dst.stride(0), x_src.data_ptr(),
+                      x_src.stride(0), att.data_ptr(), h, heads, slope, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
+                      _stream(g.device))
+    return out, lse
+
+
+def _run_gatv2_backward(g: EdgeGraph, transposed: bool, own, oth, att, heads: int, slope: float, G, lse, delta, want_datt: bool):
+    """one pygim_gatv2_backward call on ``g`` (the graph of A, or of A^T when ``transposed``) -> (d_own [g.nrows, h] in the feature dtype,
+    datt [h] in the compute dtype or None)"""
+    L, _ = _backend()
+    dt = _gather_code(own.dtype)
+    h = own.size(1)
+    d_own = torch.empty((g.nrows, h), dtype=own.dtype, device=g.device)
+    datt = torch.empty(h, dtype=att.dtype, device=g.device) if want_datt else None
+    if g.nrows == 0:
+        return d_own, None if datt is None else datt.zero_()
+    ws = _workspace(L.gatv2_backward_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
+    L.gatv2_backward(dt, 1 if transposed else 0, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, own.data_ptr(), own.stride(0), oth.data_ptr(),
+                     oth.stride(0), att.data_ptr(), h, heads, slope, G.data_ptr(), G.stride(0), lse.data_ptr(), delta.data_ptr(), d_own.data_ptr(), h,
+                     datt.data_ptr() if want_datt else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    return d_own, datt
+
+
+class GatV2Aggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, x_dst, x_src, att, heads, slope):
+        need = any(ctx.needs_input_grad[1:4])
+        out, lse = _run_gatv2_aggregate(g, x_dst, x_src, att, heads, slope, need)
+        if need:
+            ctx.g, ctx.heads, ctx.slope = g, heads, slope
+            ctx.save_for_backward(x_dst, x_src, att, out, lse)   # node-sized, all of them
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        g, heads, slope = ctx.g, ctx.heads, ctx.slope
+        x_dst, x_src, att, out, lse = ctx.saved_tensors
+        G = G.contiguous()
+        h = x_src.size(1)
+        # delta[r, k] = sum_{f in head k} G out = sum_e p dp, in the compute dtype; beside 16-bit features from the stored, once-rounded out
+        delta = (G.to(att.dtype) * out.to(att.dtype)).view(g.nrows, heads, h // heads).sum(-1).contiguous()
+        dx_dst = dx_src = datt = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
+            dx_dst, datt = _run_gatv2_backward(g, False, x_dst, x_src, att, heads, slope, G, lse, delta, ctx.needs_input_grad[3])
+            if not ctx.needs_input_grad[1]:
+                dx_dst = None
+        if ctx.needs_input_grad[2]:
+            gt, _ = g.transposed()   # the permutation is not needed: nothing per entry is stored
+            dx_src, _ = _run_gatv2_backward(gt, True, x_src, x_dst, att, heads, slope, G, lse, delta, False)
+        return None, dx_dst, dx_src, datt, None, None
+
+
+def gatv2_aggregate(graph, x_dst: torch.Tensor, x_src: torch.Tensor, att: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
+                    fused: bool = True) -> torch.Tensor:
+    """the aggregation of a GATv2 layer (Brody et al.; PyG's GATv2Conv): with ``hd = h // heads``, ``k = f // hd`` and e over the entries of row r
+
+    ``s[e, k] = sum_{f in head k} att[f] * leaky_relu(x_dst[r, f] + x_src[col[e], f], negative_slope)``
+    ``out[r, f] = sum_e softmax_e(s[., k]) * x_src[col[e], f]``
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; x_dst [rows, h] and x_src [columns, h] with ``h % heads == 0``, both
+    float32, both float64 or both the same 16-bit type; att [h] or [heads, hd] in the feature dtype, or float32 beside 16-bit features
+    (att, the sums ``z``, the scores, the softmax state and every sum are then float32 and ``out`` is rounded once per element).  Empty rows
+    give 0; duplicates are separate entries.
+    ``fused=True``: one kernel, one pass over the entries (pygim_gatv2_aggregate), one gathered row per entry; nothing of size nnz is
+    written, saved or allocated -- the forward saves ``x_dst``, ``x_src``, ``att``, ``out`` and the per-row ``lse``, the backward takes
+    ``delta = sum over a head of G * out`` in the compute dtype (beside 16-bit features from the stored, once-rounded ``out``, as
+    FlashAttention's backward does) and makes at most two pygim_gatv2_backward calls that recompute the probabilities: one on the CSR for
+    ``dx_dst`` and ``datt``, one on the transposed CSR for ``dx_src`` (no atomics, the same bits on every run).
+    ``fused=False``, and heads wider than 256 features in either case: PyG's composition -- ``z = x_dst[row] + x_src[col]``, the scores in
+    torch, ``edge_softmax``, ``spmm_values`` -- which materialises ``[nnz, h]`` tensors and keeps them for the backward.
+    Differentiable in x_dst, x_src and att, each gradient in its operand's dtype; no double backward.  Runs on the device; CPU tensors are
+    staged there and the result comes back to x_src's device."""
+    g = EdgeGraph.of(graph)
+    heads = int(heads)
+    if x_src.dtype not in FLOAT_TYPES + HALF_TYPES or x_dst.dtype != x_src.dtype:
+        raise TypeError(f"gatv2_aggregate: x_dst and x_src must both be float32, float64, bfloat16 or float16, got {x_dst.dtype} and {x_src.dtype}")
+    if att.dtype != x_src.dtype and not (x_src.dtype in HALF_TYPES and att.dtype == torch.float32):
+        raise TypeError(f"gatv2_aggregate: att must be {x_src.dtype}" + (" or float32" if x_src.dtype in HALF_TYPES else "") + f", got {att.dtype}")
+    if x_dst.dim() != 2 or x_dst.size(0) != g.nrows:
+        raise ValueError(f"gatv2_aggregate: x_dst must be [{g.nrows}, h], got {tuple(x_dst.shape)}")
+    h = x_dst.size(1)
+    if x_src.dim() != 2 or tuple(x_src.shape) != (g.ncols, h):
+        raise ValueError(f"gatv2_aggregate: x_src must be [{g.ncols}, {h}], got {tuple(x_src.shape)}")
+    if heads < 1 or h < 1 or h % heads != 0:
+        raise ValueError(f"gatv2_aggregate: heads = {heads} must divide h = {h}")
+    hd = h // heads
+    if tuple(att.shape) not in ((h,), (heads, hd)):
+        raise ValueError(f"gatv2_aggregate: att must be [{h}] or [{heads}, {hd}], got {tuple(att.shape)}")
+    slope = float(negative_slope)
+    home = x_src.device
+    ct = _compute_dtype(x_src.dtype)
+    xd, xs = x_dst.to(g.device).contiguous(), x_src.to(g.device).contiguous()
+    a = att.to(g.device, ct).reshape(h).contiguous()
+    if fused and hd <= SA_MAX_HEAD:
+        out = GatV2Aggregate.apply(g, xd, xs, a, heads, slope)
+    else:
+        row, col = g.row.long(), g.col.long()
+        z = xd.to(ct).index_select(0, row) + xs.to(ct).index_select(0, col)   # [nnz, h]
+        s = (torch.nn.functional.leaky_relu(z, slope) * a).view(g.nnz, heads, hd).sum(-1)
+        out = SpmmValues.apply(g, EdgeSoftmax.apply(g, s.contiguous(), heads), xs, heads)
     return out.to(home)

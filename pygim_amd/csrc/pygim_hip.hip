@@ -27,6 +27,7 @@
 #include "edge_softmax_dev.hpp"
 #include "gat_aggregate_dev.hpp"
 #include "sparse_attention_dev.hpp"
+#include "gatv2_dev.hpp"
 #include "spmm_reduce_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -757,6 +758,74 @@ int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, cons
         launch_sparse_attention<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
                                       (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
                                       (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_gatv2_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
+    (void)nrows;
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0 || h / heads > (int64_t)GV2_MAX_HEAD) return -1;
+    return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
+}
+
+int pygim_gatv2_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_dst, int64_t ld_dst,
+                          const void *x_src, int64_t ld_src, const void *att, int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo,
+                          void *lse, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
+    if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: heads must divide h");
+    if (h >= 1 && h / heads > (int64_t)GV2_MAX_HEAD) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: a head is at most 256 features wide");
+    if (int rc = check_csr_call("gatv2_aggregate", "rowptr / colind / x_dst / x_src / att / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll,
+                                ld_dst < ld_src ? ld_dst : ld_src, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {x_dst, nnz > 0}, {x_src, nnz > 0}, {att, nnz > 0}},
+                                pygim_gatv2_aggregate_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
+        return rc;
+    with_gather_types(dtype, [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        launch_gatv2_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_dst, (uint64_t)ld_dst,
+                                     (const S *)x_src, (uint64_t)ld_src, (const T *)att, (uint32_t)h, (uint32_t)heads, (T)negative_slope, (S *)out,
+                                     (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_gatv2_backward_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
+    (void)nrows;
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0 || h / heads > (int64_t)GV2_MAX_HEAD) return -1;
+    return (int64_t)gatv2_backward_workspace_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
+}
+
+int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_own,
+                         int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att, int64_t h, int64_t heads, double negative_slope, const void *G,
+                         int64_t ldg, const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace, int64_t workspace_bytes,
+                         void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gatv2_backward: type must be FLT32, DBL64, FLT16 or BF16");
+    if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gatv2_backward: heads must divide h");
+    if (h >= 1 && h / heads > (int64_t)GV2_MAX_HEAD) return fail(PYGIM_ERR_INVALID, "gatv2_backward: a head is at most 256 features wide");
+    if (transposed && datt) return fail(PYGIM_ERR_INVALID, "gatv2_backward: datt belongs to the call on the CSR of A (transposed = 0)");
+    if (int rc = check_csr_call("gatv2_backward", "rowptr / colind / x_own / x_oth / att / G / lse / delta / d_own", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll,
+                                ld_own < ld_oth ? ld_own : ld_oth, ldg < ldd ? ldg : ldd,
+                                {{rowptr, true}, {d_own, nrows > 0}, {datt, true, true}, {colind, nnz > 0}, {x_own, nnz > 0}, {x_oth, nnz > 0},
+                                 {att, nnz > 0}, {G, nnz > 0}, {lse, nnz > 0}, {delta, nnz > 0}},
+                                pygim_gatv2_backward_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
+        return rc;
+    with_gather_types(dtype, [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        if (transposed)
+            launch_gatv2_backward<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_own,
+                                              (uint64_t)ld_own, (const S *)x_oth, (uint64_t)ld_oth, (const T *)att, (uint32_t)h, (uint32_t)heads,
+                                              (T)negative_slope, (const S *)G, (uint64_t)ldg, (const T *)lse, (const T *)delta, (S *)d_own, (uint64_t)ldd,
+                                              nullptr, workspace, (hipStream_t)stream);
+        else
+            launch_gatv2_backward<T, S, false>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_own,
+                                               (uint64_t)ld_own, (const S *)x_oth, (uint64_t)ld_oth, (const T *)att, (uint32_t)h, (uint32_t)heads,
+                                               (T)negative_slope, (const S *)G, (uint64_t)ldg, (const T *)lse, (const T *)delta, (S *)d_own, (uint64_t)ldd,
+                                               (T *)datt, workspace, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;

@@ -21,6 +21,10 @@ kernel, no ``[nnz, heads]`` tensor written or kept for the backward.  The defaul
 TransformerConv / GraphTransformer are the dot-product attention layer (PyG's TransformerConv without edge features or ``beta``) on
 ``pygim_amd.attention.sparse_attention``: one kernel per layer when ``fused`` is set, the three-pass composition otherwise; the same
 dtypes as GATConv.
+
+GATv2Conv / GATv2 are PyG's GATv2Conv (Brody et al.) without self loops or edge features on ``pygim_amd.attention.gatv2_aggregate``: fused by
+default -- one forward kernel and two backward kernels per layer, nothing of size nnz -- because the composition holds ``[nnz, heads * out]``
+tensors; the same dtypes as GATConv.
 """
 import torch
 import torch.nn.functional as F
@@ -141,6 +145,40 @@ class TransformerConv(torch.nn.Module):
         return out if self.lin_skip is None else out + self.lin_skip(x)
 
 
+class GATv2Conv(torch.nn.Module):
+    """PyG's GATv2Conv arithmetic on the adjacency as given (no self loops are inserted, no edge features): x_l = lin_l(x) (the source /
+    value side) and x_r = lin_r(x) (the target side) as [N, H, F], ``lin_r is lin_l`` with ``share_weights``;  score of stored entry
+    (i, j) = (att * leaky_relu(x_r[i] + x_l[j])).sum(-1) per head;  p = softmax of the scores over the entries of row i;
+    out[i] = sum_j p[(i, j)] * x_l[j] per head; heads concatenated or averaged; + bias.
+    ``fused=True`` (the default): everything after the two linear maps is ``gatv2_aggregate``'s fused forward and backward (heads wider
+    than 256 features run unfused); ``fused=False`` materialises ``[nnz, H * F]``."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, fused=True, **_):
+        super().__init__()
+        self.fused, self.share_weights = bool(fused), bool(share_weights)
+        self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
+        self.lin_l = Linear(in_channels, self.heads * self.out_channels, bias=bias)
+        self.lin_r = self.lin_l if self.share_weights else Linear(in_channels, self.heads * self.out_channels, bias=bias)
+        self.att = torch.nn.Parameter(torch.empty(self.heads, self.out_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(self.heads * self.out_channels if self.concat else self.out_channels)) if bias else None
+        torch.nn.init.xavier_uniform_(self.lin_l.weight)
+        if not self.share_weights:
+            torch.nn.init.xavier_uniform_(self.lin_r.weight)
+        torch.nn.init.xavier_uniform_(self.att)
+
+    def forward(self, x, adj_t):
+        from .attention import EdgeGraph, gatv2_aggregate
+
+        g = EdgeGraph.of(adj_t)
+        x_l = self.lin_l(x)
+        x_r = x_l if self.share_weights else self.lin_r(x)
+        att = self.att if self.att.dtype == x_l.dtype else self.att.float()   # autocast: 16-bit features beside the float32 parameter
+        out = gatv2_aggregate(g, x_r, x_l, att, heads=self.heads, negative_slope=self.negative_slope, fused=self.fused)
+        if not self.concat:
+            out = out.view(-1, self.heads, self.out_channels).mean(1)
+        return out if self.bias is None else out + self.bias
+
+
 def folded_epilogue(conv_bias, bn):
     """bias + eval-mode BatchNorm as ONE affine map per feature: bn(y + bias) = a * y + b with
     a = weight / sqrt(running_var + eps), b = (bias - running_mean) * a + bn.bias"""
@@ -196,6 +234,13 @@ class GAT(_Stack):
         assert hidden_channels % heads == 0, "GAT: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
                          lambda h: GATConv(h, h // heads, heads=heads, concat=True, fused=fused))
+
+
+class GATv2(_Stack):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, share_weights=False, fused=True):
+        assert hidden_channels % heads == 0, "GATv2: heads must divide hidden_channels (the heads are concatenated)"
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: GATv2Conv(h, h // heads, heads=heads, concat=True, share_weights=share_weights, fused=fused))
 
 
 class GraphTransformer(_Stack):

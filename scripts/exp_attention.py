@@ -19,7 +19,13 @@ warm-up.  JSON lines:
     Q, K, V (--dtypes), two rounds: (a) sparse_attention forward without and with lse; (b) the three-pass composition -- one pygim_sddmm
     per head, edge_softmax, spmm_values; (c) gat_aggregate at the same heads; (d) spmm_values twice, the floor of the gather (every
     entry reads one K row and one V row); then forward + backward of both paths with torch.cuda.max_memory_allocated for each.
-    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot] [--forward-only] [--dtypes f32,bf16,f16]
+  the GATv2 aggregation (--section v2, on its own: profiles/exp_gatv2.txt), heads = 1 and 8, FLT32 and BF16 storage of x_dst, x_src
+    (--dtypes), two rounds: (a) gatv2_aggregate forward without and with lse; (b) gat_aggregate and (c) sparse_attention at the same
+    heads, from the same run; then forward + backward of the fused path with torch.cuda.max_memory_allocated, and each of the two
+    pygim_gatv2_backward calls on its own.  There is no composition to compare with on this graph (one [nnz, h] float32 tensor is
+    nnz * h * 4 bytes = 117 GB); fused against fused=False runs on --small-shape (products-mini: 1 000 000 entries, one [nnz, h] float32
+    tensor = 1.02 GB, so the handful the composition and its autograd graph hold fit beside everything else).
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot|v2] [--forward-only] [--dtypes f32,bf16,f16]
   --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
   (profiles/exp_gat_fused.txt); all = base + fused."""
 import argparse
@@ -230,6 +236,101 @@ def dot_section(g, n, nnz, h, iters, dev, line, names, backward=True):
     line(what="sparse_attention workspace bytes", heads8=_lib.sparse_attention_workspace(_lib.FLT32, n, nnz, h, 8))
 
 
+def v2_section(g, n, nnz, h, iters, dev, line, names, small_shape, backward=True):
+    """the GATv2 aggregation next to gat_aggregate and sparse_attention; fused against the composition on a graph where that fits"""
+    g.transposed()   # built once per graph, before any backward is measured
+    slope = 0.2
+    d32, s32, g32 = (synth.features(n, h, torch.float32, seed=sd, device=dev, kind="uniform") for sd in (5, 6, 8))
+    for name in names:
+        dt = HALF_DTYPES[name]
+        Xd, Xs, G = (t.to(dt) for t in (d32, s32, g32))
+        for heads in (1, 8):
+            hd = h // heads
+            gen = torch.Generator(device=dev).manual_seed(4)
+            a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+            a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+            att = torch.randn(h, device=dev, generator=gen) * hd ** -0.5
+            for rnd in range(2):
+                ta = timed(lambda: attention._run_gatv2_aggregate(g, Xd, Xs, att, heads, slope, False), iters)
+                tl = timed(lambda: attention._run_gatv2_aggregate(g, Xd, Xs, att, heads, slope, True), iters)
+                tg = timed(lambda: attention._run_gat_aggregate(g, a_dst, a_src, Xs, heads, slope, False), iters)
+                ts = timed(lambda: attention._run_sparse_attention(g, Xd, Xs, Xs, heads, hd ** -0.5, False), iters)
+                line(what="gatv2_aggregate forward", x_dtype=name, heads=heads, round=rnd, a_gatv2_aggregate_ms=round(ta, 3), a_with_lse_ms=round(tl, 3),
+                     b_gat_aggregate_ms=round(tg, 3), c_sparse_attention_ms=round(ts, 3), a_over_b=round(ta / tg, 4), a_over_c=round(ta / ts, 4),
+                     gather_tb_s=round(nnz * h * Xs.element_size() / ta / 1e9, 2))
+            if not backward:
+                continue
+            out, lse = attention._run_gatv2_aggregate(g, Xd, Xs, att, heads, slope, True)
+            delta = (G.float() * out.float()).view(n, heads, hd).sum(-1).contiguous()
+            gt, _ = g.transposed()
+            nb = max(2, iters // 3)
+            t_row = timed(lambda: attention._run_gatv2_backward(g, False, Xd, Xs, att, heads, slope, G, lse, delta, True), nb)
+            t_col = timed(lambda: attention._run_gatv2_backward(gt, True, Xs, Xd, att, heads, slope, G, lse, delta, False), nb)
+            del out, lse, delta
+            leaves = [t.clone().requires_grad_() for t in (Xd, Xs, att)]
+
+            def step():
+                for t in leaves:
+                    t.grad = None
+                attention.gatv2_aggregate(g, *leaves, heads=heads, negative_slope=slope).backward(G)
+
+            step()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            ms = timed(step, nb)
+            peak = torch.cuda.max_memory_allocated()
+            del leaves
+            line(what="gatv2_aggregate forward + backward", x_dtype=name, heads=heads, fused_ms=round(ms, 2), backward_row_side_ms=round(t_row, 2),
+                 backward_transposed_ms=round(t_col, 2), fused_peak_above_start_gb=round((peak - base) / 1e9, 2),
+                 one_nnz_h_float32_tensor_gb=round(nnz * h * 4 / 1e9, 2),
+                 backward_workspace_gb=round(_lib.gatv2_backward_workspace(_lib.FLT32, n, nnz, h, heads) / 1e9, 2))
+        del Xd, Xs, G
+    del d32, s32, g32
+    line(what="gatv2 workspace bytes", aggregate_heads8=_lib.gatv2_aggregate_workspace(_lib.FLT32, n, nnz, h, 8),
+         backward_heads8=_lib.gatv2_backward_workspace(_lib.FLT32, n, nnz, h, 8))
+    if not backward:
+        return
+    # fused against the composition, where the composition fits
+    ns, nnzs, d_max = synth.SHAPES[small_shape]
+    rowptr, col = synth.make_csr(ns, nnzs, d_max, seed=0, device=dev)
+    gs = attention.EdgeGraph(rowptr, col, (ns, ns))
+    gs.transposed()
+    d32, s32, g32 = (synth.features(ns, h, torch.float32, seed=sd, device=dev, kind="uniform") for sd in (5, 6, 8))
+    for name in names:
+        dt = HALF_DTYPES[name]
+        for heads in (1, 8):
+            att = torch.randn(h, device=dev, generator=torch.Generator(device=dev).manual_seed(4)) * (h // heads) ** -0.5
+            leaves = [t.clone().requires_grad_() for t in (d32.to(dt), s32.to(dt), att)]
+            G = g32.to(dt)
+            res, outs = {}, {}
+            for path, fused in (("fused", True), ("unfused", False)):
+                def step():
+                    for t in leaves:
+                        t.grad = None
+                    out = attention.gatv2_aggregate(gs, *leaves, heads=heads, negative_slope=slope, fused=fused)
+                    out.backward(G)
+                    return out
+
+                outs[path] = [step().detach().float()] + [t.grad.float().clone() for t in leaves]
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                ms = timed(step, max(2, iters // 3))
+                res[path] = (ms, base, torch.cuda.max_memory_allocated())
+            # largest difference between the two paths per tensor, relative to the tensor's largest magnitude
+            diff = {k: float("%.2e" % ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item())
+                    for k, a, b in zip(("out", "dx_dst", "dx_src", "datt"), outs["fused"], outs["unfused"])}
+            del leaves, outs
+            line(what="gatv2_aggregate fused vs composition, forward + backward", graph=small_shape, nnz=nnzs, x_dtype=name, heads=heads,
+                 fused_ms=round(res["fused"][0], 2), unfused_ms=round(res["unfused"][0], 2),
+                 fused_peak_above_start_gb=round((res["fused"][2] - res["fused"][1]) / 1e9, 3),
+                 unfused_peak_above_start_gb=round((res["unfused"][2] - res["unfused"][1]) / 1e9, 3),
+                 one_nnz_h_float32_tensor_gb=round(nnzs * h * 4 / 1e9, 2), max_diff_over_max_magnitude=diff)
+
+
 def base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line):
     """spmm_values, edge_softmax, the workspaces, new values through a new group: the record in profiles/exp_attention.txt"""
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -316,7 +417,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot"])
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot", "v2"])
+    ap.add_argument("--small-shape", default="products-mini", help="--section v2: the graph on which fused=False fits in memory")
     ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half / dot: the storage types of the features to measure")
     ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
     args = ap.parse_args()
@@ -342,6 +444,10 @@ def main():
     if args.section == "dot":
         del x
         dot_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")], backward=not args.forward_only)
+    if args.section == "v2":
+        del x
+        v2_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")], args.small_shape,
+                   backward=not args.forward_only)
     torch.ops.pim_ops.dpu_release()
 
 
