@@ -435,8 +435,11 @@ int pygim_group_host_windows(int64_t handle, int64_t *windows, int64_t *direct);
 /* geometry of that schedule, as the library planned it (callers price staged bytes from THIS, not from assumed constants):
  * waves per workgroup, accumulators (rows) per wave, columns per chunk (chunk bytes = 256 x this), chunk buffers of the LDS ring,
  * staged columns per group of reads and x-register sets of a code stream (0 0 for a token plan), stored entries served by another
- * entry's LDS read (code streams: entries of different rows of one wave that share a column of a chunk), column ranges per row tile */
-int pygim_group_lds_geometry(int64_t handle, int64_t out[8]);
+ * entry's LDS read (code streams: entries of different rows of one wave that share a column of a chunk), column ranges per row tile,
+ * slices of X an XCD runs side by side in a product of the group's full width (1, 2 or 4: "lds_xcd_slices"), and whether the workgroups that
+ * run one code stream side by side share its touches ("lds_touch_share": 1 = one wave pulls a stream's lines into the L2, its partners ask for
+ * one dword per touch; 0 = every wave touches every line -- also what a plan reports whose x registers reach the touch register) */
+int pygim_group_lds_geometry(int64_t handle, int64_t out[10]);
 /* which form of the product the group got at creation and, when it is not the fastest one, why (text, NUL-terminated, at most cap - 1
  * characters): "code-stream form" | "code-stream form not available: <reason>; products take the token form ..." | "... the L2 sweep
  * serves this group".  The ladder is code stream -> token kernels -> sweep; nothing falls back silently. */
@@ -461,7 +464,7 @@ int pygim_group_lds_note(int64_t handle, char *out, int64_t cap);
  * reads run nsets - 1 groups ahead of the adds; 0 = default), "lds_codegen" (code streams: 1 = generated on the device from the resident CSR -- the default --, 0 = by
  * the host encoder, 2 = on the device and checked word for word against the host encoder), "lds_tile_order" (which rows share a tile: 0 = consecutive
  * rows, 1 = rows ordered by similarity, 2 = automatic: similarity for square parts of a million entries and more), "lds_lp_rounds", "lds_hybrid" (density split of a community-structured part whose ids carry no locality: the dense (tile, chunk) cells through the LDS-staged kernel, the rest through the sweep; 0 = off, 1 = integer types, 2 = floats too -- their sums are then reordered), "lds_hybrid_min" (entries a cell must hold), "lds_xcd_slices" (code-stream products: slices of X per XCD -- 0 = automatic (the default), 1 = an XCD streams one slice through
- * its L2; 2 / 4 = the workgroups an XCD runs side by side are slices of the same tile and share its code stream in L2), "lds_long_slots", "lds_ablate" (timing experiments, wrong results)};
+ * its L2; 2 / 4 = the workgroups an XCD runs side by side are slices of the same tile and share its code stream in L2), "lds_touch_share" (8-wave code-stream products with 2 / 4 slices per XCD: 1 = the workgroups that run one stream side by side share its touches -- the default --, 0 = every wave touches), "lds_long_slots", "lds_ablate" (timing experiments, wrong results)};
  * returns the previous value, or -1 for an unknown name (pygim_last_error() says which).
  * READ AT GROUP CREATION (they shape the plan; changing them afterwards does not touch existing groups, and switching "lds_code" off
  * after a code-stream group was created sends that group's products to the sweep): panel_*, long_*, split_unit_pattern, narrow_vals,

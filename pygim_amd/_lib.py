@@ -420,9 +420,10 @@ def group_host_call(handle):
 
 
 def group_lds_geometry(handle):
-    out = (ctypes.c_int64 * 8)()
+    out = (ctypes.c_int64 * 10)()
     check(lib().pygim_group_lds_geometry(int(handle), out))
-    return dict(zip(["waves", "acc_per_wave", "chunk_cols", "buffers", "group", "x_sets", "shared_entries", "col_splits"], [int(v) for v in out]))
+    return dict(zip(["waves", "acc_per_wave", "chunk_cols", "buffers", "group", "x_sets", "shared_entries", "col_splits", "xcd_slices", "touch_share"],
+                    [int(v) for v in out]))
 
 
 def group_lds_note(handle):

@@ -56,7 +56,7 @@ struct CgParams {
     uint32_t half_H = 0;                            // half-split plans (LdsGeometry::half_split): column c of the matrix is the VIRTUAL column c mod H, staged beside its twin in one
                                                     // 256-byte row; ncols (above) = H; an entry's half (c >= H) rides in the sorted payload and picks the EXEC mask of its add
     // register map (LdsCodeRegs)
-    uint32_t x0 = 6, acc0 = 28, vbase0 = 1, vbase1 = 2, vbase2 = 3, vl16 = 4, vtouch = 4, vjunk = 5;
+    uint32_t x0 = 6, acc0 = 28, vbase0 = 1, vbase1 = 2, vbase2 = 3, vl16 = 4, vtouch = LDS_CODE8_VTOUCH, vjunk = 5;
     uint32_t s_xs = 80, s_ldsw = 82, s_cb = 84, s_ret = 86, s_pa = 92;
     PYGIM_HD uint32_t vbase(uint32_t blk) const { return blk == 0 ? vbase0 : blk == 1 ? vbase1 : vbase2; }
 };

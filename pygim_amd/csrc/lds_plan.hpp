@@ -385,8 +385,10 @@ struct LdsCodeRegs {
     constexpr uint32_t nx() const { return gsize * nsets * (wide ? 2 : 1); }   // x REGISTERS
 };
 // 16 waves: v4 v5 v10 bases, v6 lane * 16, v11 (lane % 8) * 128, v9 junk, x v12..v27, accumulators v28..v123
-// 8 waves:  v0 is the lane id (the only register the compiler keeps), v1..v3 bases, v4 lane * 16 (DMA and touch), v5 junk,
-//           x v6..v27 (22 registers: two sets of 10 or three of 6), accumulators v28..v255
+// 8 waves:  v0 is the lane id (the only register the compiler keeps), v1..v3 bases, v4 lane * 16 (DMA), v5 junk,
+//           x v6..v27 (22 registers: two sets of 10 or three of 6), accumulators v28..v255; the touch offset is v27 when the x registers
+//           end below it (lane * 16 in a toucher, 0 in a wave whose partner workgroup touches), else v4
+constexpr uint32_t LDS_CODE8_VTOUCH = 27;
 constexpr LdsCodeRegs lds_code_regs(uint32_t NW, uint32_t gsize = 0, uint32_t nsets = 0, bool wide = false) {
     LdsCodeRegs r;
     r.wide = wide ? 1 : 0;
@@ -405,8 +407,13 @@ constexpr LdsCodeRegs lds_code_regs(uint32_t NW, uint32_t gsize = 0, uint32_t ns
     if (r.gsize < 2) r.gsize = 2;
     if (r.nsets < 2) r.nsets = 2;
     while (r.x0 + r.nx() > r.acc0 && r.gsize > 2) r.gsize -= wide ? 1 : 2;
+    // 8 waves: the touch offset lives in v27 whenever the x registers leave it free (2 x 10, 3 x 6, 2 x 5 pairs: v6..v25 at most) -- the shell sets it
+    // per WORKGROUP, so that of the workgroups that run one stream side by side only one pulls its lines through the L1 (LdsArgs.touch_share)
+    if (NW != 16 && r.x0 + r.nx() <= LDS_CODE8_VTOUCH) r.vtouch = LDS_CODE8_VTOUCH;
     return r;
 }
+// a plan whose touches go through the register that the shell sets per workgroup
+constexpr bool lds_code_touch_shareable(const LdsCodeRegs &r) { return r.vtouch != r.vl16 && r.vtouch == LDS_CODE8_VTOUCH; }
 // what build_lds_plan chooses when the tunables leave it open (measured: profiles/r04_lds_kernel.md)
 constexpr uint32_t LDS_CODE_AUTO_WAVES = 8, LDS_CODE8_AUTO_NBUF = 5;
 constexpr uint32_t LDS_CODE8_KA64 = 114;  // ... of its 8-byte form: a register pair per accumulator

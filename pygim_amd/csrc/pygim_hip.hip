@@ -190,6 +190,7 @@ int64_t pygim_set_tunable(const char *name, int64_t value) {
     else if (n == "lds_hybrid_contig") slot = &g_tune.lds_hybrid_contig;
     else if (n == "lds_code_boundary") slot = &g_tune.lds_code_boundary;
     else if (n == "lds_xcd_slices") slot = &g_tune.lds_xcd_slices;
+    else if (n == "lds_touch_share") slot = &g_tune.lds_touch_share;
     else if (n == "lds_codegen") slot = &g_tune.lds_codegen;
     else if (n == "lds_tile_order") slot = &g_tune.lds_tile_order;
     else if (n == "lds_lp_rounds") slot = &g_tune.lds_lp_rounds;
@@ -1036,11 +1037,11 @@ int pygim_group_host_windows(int64_t handle, int64_t *windows, int64_t *direct) 
     return 0;
 }
 
-int pygim_group_lds_geometry(int64_t handle, int64_t out[8]) {
+int pygim_group_lds_geometry(int64_t handle, int64_t out[10]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
     const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
-    for (int i = 0; i < 8; i++) out[i] = 0;
+    for (int i = 0; i < 10; i++) out[i] = 0;
     if (!p.lds_tiles) return 0;
     out[0] = p.lds_nw;
     out[1] = p.lds_ka;
@@ -1050,6 +1051,13 @@ int pygim_group_lds_geometry(int64_t handle, int64_t out[8]) {
     out[5] = p.lds_is_code ? p.lds_code_nsets : 0;
     out[6] = p.lds_is_code ? (int64_t)p.lds_code_shared : 0;
     out[7] = p.lds_col_splits;
+    // a product of the group's full width, as launch_lds lays it over the XCDs under the tunables of this moment
+    const size_t es = dtype_size(g->dtype);
+    const uint32_t eps = es == 1 ? 128u : (uint32_t)((es == 8 ? 512 : 256) / std::max<size_t>(es, 1));
+    const uint32_t nslices = p.lds_half ? 1u : (uint32_t)((std::max<int64_t>(g->h, 1) + eps - 1) / eps);
+    const LdsXcdLayout lay = lds_xcd_layout(p, nslices, es == 8);
+    out[8] = lay.sx;
+    out[9] = lay.touch_share;
     return 0;
 }
 

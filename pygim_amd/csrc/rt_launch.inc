@@ -281,6 +281,44 @@ int launch_block_t(Group *g, Part &p, const T *X, int64_t ldx, T *C, int64_t ldc
     return join();
 }
 
+// How a launch of the LDS-staged kernel lays its workgroups over the XCDs: group = XCDs that share the tiles of one set of slices (0 = no
+// XCD mapping: slice counts that do not divide 8), sx = slices per XCD, touch_share = the sx workgroups that run a tile's code streams side
+// by side share the touches (LdsArgs.touch_share).  One rule for the launch and for what pygim_group_lds_geometry reports.
+struct LdsXcdLayout {
+    uint32_t group = 0, sx = 1, touch_share = 0;
+};
+static LdsXcdLayout lds_xcd_layout(const Part &p, uint32_t nslices, bool el8) {
+    LdsXcdLayout l;
+    // (slice counts that do not divide 8 interleave the slices over the XCDs; a slice-major order measured the same: 2.86 vs 2.80 ms at h = 192)
+    l.group = (nslices == 1 || nslices == 2 || nslices == 4 || nslices == 8) ? 8 / nslices : 0;
+    // round 5 (VERDICT r04 item 3): sx slices per XCD -- the workgroups an XCD runs side by side are then the sx slices of ONE tile and
+    // share its code stream in that XCD's L2 (fetched from the fabric nslices / sx times instead of nslices), at the price of sx
+    // slices of X streamed through every L2 instead of one
+    if (l.group && p.lds_is_code && nslices > 1) {
+        // 0 = automatic (profiles/r05_exp_xcd.txt): two slices per XCD -- fabric traffic 5.28 -> 4.19 GB on the bench workload --
+        // and all (up to four) of them for plans whose tiles skip most chunks (little of X to un-share): 5.57 -> 3.72 GB, 1.05 -> 0.98 ms
+        uint32_t sx = (uint32_t)std::max<int64_t>(0, g_tune.lds_xcd_slices);
+        if (sx == 0) {
+            const uint64_t nchunks = ((uint64_t)p.ncols + p.lds_kc - 1) / std::max(1u, p.lds_kc);
+            const double fill = p.lds_ntiles && nchunks ? (double)p.lds_slots / ((double)p.lds_ntiles * (double)nchunks) : 1.0;
+            sx = fill < 0.3 ? std::min(nslices, 4u) : (el8 ? 1u : 2u);   // (8-byte rows: one slice per XCD measured 1 % ahead, 7.05-7.13 against 7.17-7.18 ms)
+            // (plans that stream every chunk, with the touches shared -- profiles/exp_touch_share.txt, bench workload: two slices 2.04 -> 1.97 ms, four 2.10 -> 1.99:
+            // the pair stays the fastest arrangement, the second pair's slices of X cost more than its touches save)
+        }
+        if (sx > 1 && sx <= nslices && nslices % sx == 0) {
+            l.sx = sx;
+            l.group *= sx;
+        }
+    }
+    // the partners of a toucher ask for one dword per touch instead of eight lines (L1 -> L2 read requests of the bench workload 271.5 M -> 257.0 M per product,
+    // 2.04 -> 1.97 ms): only the 8-wave shells set the touch register per workgroup, and only plans whose x registers leave it free touch through it
+    // (lds_plan.hpp lds_code_regs)
+    if (l.sx > 1 && g_tune.lds_touch_share && p.lds_is_code && p.lds_nw == 8 &&
+        lds_code_touch_shareable(lds_code_regs(8, p.lds_code_gsize, p.lds_code_nsets, p.lds_row_bytes == 512)))
+        l.touch_share = 1;
+    return l;
+}
+
 // LDS-staged product (lds_kernel_gen.hpp / lds_plan.hpp): X is copied slice-major in 256-byte slices (64 features, rows padded to
 // whole 256-column chunks), then ONE launch: a 512-thread workgroup per (tile of rows, slice) streams the tile's chunks of X
 // through a double-buffered 160 KiB LDS ring (two chunks of 320 columns) and keeps the tile's running sums in registers; C is written once.
@@ -411,26 +449,10 @@ int launch_lds(Group *g, Part &p, const T *X, int64_t ldx, T *C, int64_t ldc, ui
     a.post_mul = kernel_amax ? g->post_mul : nullptr;   // (the per-column epilogue rides the dequantising store only)
     a.post_add = kernel_amax ? g->post_add : nullptr;
     a.post_relu = kernel_amax ? g->post_relu : 0;
-    // (slice counts that do not divide 8 interleave the slices over the XCDs; a slice-major order measured the same: 2.86 vs 2.80 ms at h = 192)
-    a.xcd_group = (nslices == 1 || nslices == 2 || nslices == 4 || nslices == 8) ? 8 / nslices : 0;
-    a.xcd_sx = 1;
-    // round 5 (VERDICT r04 item 3): sx slices per XCD -- the workgroups an XCD runs side by side are then the sx slices of ONE tile and
-    // share its code stream in that XCD's L2 (fetched from the fabric nslices / sx times instead of nslices), at the price of sx
-    // slices of X streamed through every L2 instead of one
-    if (a.xcd_group && p.lds_is_code && nslices > 1) {
-        // 0 = automatic (profiles/r05_exp_xcd.txt): two slices per XCD -- fabric traffic 5.28 -> 4.19 GB on the bench workload --
-        // and all (up to four) of them for plans whose tiles skip most chunks (little of X to un-share): 5.57 -> 3.72 GB, 1.05 -> 0.98 ms
-        uint32_t sx = (uint32_t)std::max<int64_t>(0, g_tune.lds_xcd_slices);
-        if (sx == 0) {
-            const uint64_t nchunks = ((uint64_t)p.ncols + p.lds_kc - 1) / std::max(1u, p.lds_kc);
-            const double fill = p.lds_ntiles && nchunks ? (double)p.lds_slots / ((double)p.lds_ntiles * (double)nchunks) : 1.0;
-            sx = fill < 0.3 ? std::min(nslices, 4u) : (EL8 ? 1u : 2u);   // (8-byte rows: one slice per XCD measured 1 % ahead, 7.05-7.13 against 7.17-7.18 ms)
-        }
-        if (sx > 1 && sx <= nslices && nslices % sx == 0) {
-            a.xcd_sx = sx;
-            a.xcd_group *= sx;
-        }
-    }
+    const LdsXcdLayout lay = lds_xcd_layout(p, nslices, EL8);
+    a.xcd_group = lay.group;
+    a.xcd_sx = lay.sx;
+    a.touch_share = lay.touch_share;
     a.half_split = HS ? 1u : 0u;
     a.xcd_contig = (a.xcd_group && p.lds_contig_tiles) ? (p.lds_ntiles + a.xcd_group - 1) / a.xcd_group : 0;
     const uint32_t grid = a.xcd_group ? 8 * ((p.lds_ntiles + a.xcd_group - 1) / a.xcd_group) * a.xcd_sx : p.lds_ntiles * nslices;

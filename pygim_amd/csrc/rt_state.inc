@@ -92,6 +92,8 @@ struct Tunables {
     int64_t lds_lp_rounds = 12;         // rounds of the label propagation (products-shaped SBM: 3 271 labels after 6, 882 after 12 -- 1 200 planted; sweep 11.7 -> 10.9 ms)
     int64_t lds_codegen = 1;            // code streams: 1 = generated on the device from the resident CSR (lds_codegen_dev.hpp), 0 = by the host encoder, 2 = on the device AND checked word for word against the host encoder (tests)
     int64_t lds_xcd_slices = 0;         // code-stream kernels: slices of X per XCD (0 = automatic; 1 = an XCD streams one slice; 2 / 4: a tile's slices side by side on one XCD share its code in L2)
+    int64_t lds_touch_share = 1;        // 8-wave code-stream kernels with 2 / 4 slices per XCD: 1 = of the workgroups that run one stream side by side a single wave pulls its lines
+                                        // through the L1 ahead of the sequencer, its partners' touches ask for one dword (LdsArgs.touch_share); 0 = every wave touches every line
     int64_t lds_code_boundary = 0;      // rings of >= 3 buffers: 0 / 1 = the workgroup meets at the slot boundary (one more chunk in flight, the last group's adds cross the barrier), 2 = in the middle of a slot
     int64_t lds_code_exp = 0;           // (timing experiments, WRONG results) code streams without barriers (1) / without the chunk DMA (2)
     int64_t lds_hybrid = 1;             // density split of community-structured parts (lds_hybrid_dev.hpp): 0 off, 1 integer types (exact), 2 floats too (the order of a row's sums changes)

@@ -62,8 +62,10 @@ GEO_CODE = Geo(16, 96, 8, 4)                 # the code-stream kernels: chunks o
 GEO_CODE.pieces = 48 // 16
 # the 8-wave code-stream kernels (round 4): 228 accumulators per wave, 2 waves per SIMD with 256 VGPRs each -- 1 824-row tiles, so that
 # the Reddit-shaped product of four slices is two rounds of workgroups instead of three.  Register map = lds_plan.hpp lds_code_regs(8):
-# v0 lane id (the compiler's), v1..v3 LDS bases, v4 lane * 16 (DMA and touch), v5 touch destination, x v6..v27, accumulators v28..v255;
+# v0 lane id (the compiler's), v1..v3 LDS bases, v4 lane * 16 (DMA; the touch offset too when the x registers reach v27), v5 touch destination,
+# x v6..v27, accumulators v28..v255; v27 = the touch offset of plans whose x registers end below it (VTOUCH8, set per workgroup: body());
 # the store stage borrows x registers (v8, v9 temporaries; v6, v7 epilogue factors)
+VTOUCH8 = 27
 GEO_CODE8 = Geo(8, 228, 8, 1, regmap=("v1", "v2", "v4", "v1", "v8", "v9", "v3", "v4"), X0=6, ACC0=28, dummy=False)
 GEO_CODE8.pieces = 0   # (taken from the plan: LdsArgs.piece_bytes)
 # ... and its 8-byte form (INT64 / DBL64): 114 rows per wave, a register pair per running sum, rows of 512 bytes in LDS (lane * 8)
@@ -128,6 +130,12 @@ def body(op_add, g, ablate=0, op_mul=None, deq=None, code=False, out_kind=None, 
     if VL128 != VL16:
         a(f"v_lshlrev_b32 {VL128}, 7, %[lane]")
     a(f"v_lshlrev_b32 {VL16}, 4, %[lane]")
+    if code and g.regmap:
+        # 8-wave code streams touch their own lines through v27 (lds_plan.hpp lds_code_regs).  Workgroups that run ONE stream side by side on an XCD
+        # (LdsArgs.xcd_sx > 1) share the touches (LdsArgs.touch_share): [tmul] is 16 in the wave that touches stream (tile, wave) -- v27 = lane * 16, the
+        # 8 lines 2 KiB ahead -- and 0 in its partners' -- v27 = 0: one dword of a line the toucher fetches.  The load still issues and still
+        # counts in vmcnt, so the stream's literal wait counts hold.  (A plan whose x registers reach v27 touches with v4 and overwrites this.)
+        a(f"v_mul_u32_u24 v{VTOUCH8}, %[tmul], %[lane]")
     a(f"v_mov_b32 {VM}, 0x3ff00")
     a(f"v_lshlrev_b32 {VB}, {g.lane_shift}, %[lane]")       # (the token carries the LDS row of both buffers: the lane offset is all that is added)
     a(f"v_mov_b32 {VZ}, 0")
@@ -613,7 +621,9 @@ constexpr uint32_t LDS_L16_KA = %(KAL)du, LDS_L16_BATCH = %(BL)du;
 static_assert(lds_code_regs(16).vbase[0] == 4 && lds_code_regs(16).vbase[1] == 5 && lds_code_regs(16).vbase[2] == 10 && lds_code_regs(16).vl16 == 6 &&
               lds_code_regs(16).vtouch == 11 && lds_code_regs(16).vjunk == 9 && lds_code_regs(16).x0 == 12 && lds_code_regs(16).acc0 == 28, "16-wave code map");
 static_assert(lds_code_regs(8).vbase[0] == 1 && lds_code_regs(8).vbase[1] == 2 && lds_code_regs(8).vbase[2] == 3 && lds_code_regs(8).vl16 == 4 &&
-              lds_code_regs(8).vtouch == 4 && lds_code_regs(8).vjunk == 5 && lds_code_regs(8).x0 == 6 && lds_code_regs(8).acc0 == 28 &&
+              lds_code_regs(8).vtouch == %(VT8)d && lds_code_regs(8, 0, 0, true).vtouch == %(VT8)d && lds_code_regs(8, 6, 3).vtouch == %(VT8)d &&
+              lds_code_regs(8, 2, 11).vtouch == 4 && LDS_CODE8_VTOUCH == %(VT8)d && LDS_CODE8_VTOUCH < lds_code_regs(8).acc0 &&
+              lds_code_regs(8).vjunk == 5 && lds_code_regs(8).x0 == 6 && lds_code_regs(8).acc0 == 28 &&
               LDS_CODE8_KA == %(KAC8)d, "8-wave code map");
 
 struct LdsArgs {
@@ -638,6 +648,8 @@ struct LdsArgs {
     uint64_t *stamps;                  // measurement build (k_lds_code8_f32_ts): four 100 MHz clock values per wave (start, stream entered, stream left, stored)
     uint32_t xcd_contig;               // 0 = an XCD takes every xcd_group-th tile; T > 0 = a contiguous run of T tiles (plans whose neighbouring tiles stage the
                                        // same chunks -- the dense half of a density split: they then meet in that XCD's L2)
+    uint32_t touch_share;              // 8-wave code streams with xcd_sx > 1: 1 = of the xcd_sx workgroups that run a tile's streams side by side, wave w of the
+                                       // one at slice position w %% xcd_sx touches stream (tile, w) and its partners ask for one dword per touch; 0 = every wave touches
 };
 """
 
@@ -647,11 +659,13 @@ __global__ __launch_bounds__(%(threads)d) void %(name)s(LdsArgs a) {
     extern __shared__ char lds_dyn[];
     constexpr uint32_t NW = %(NW)d, KA = %(KA)d, BATCH = %(BATCH)d, PIECE = %(piece)du;
     const uint32_t b = blockIdx.x;
-    uint32_t slice, ti;
+    uint32_t slice, ti, spos = 0, sxn = 1;   // (position among the sxn workgroups that run this tile side by side)
     if (a.xcd_group) {  // blocks b and b + 8 share an XCD: a group of xcd_group XCDs streams xcd_sx slices of X through its L2s; with
                         // xcd_sx > 1 workgroups i, i + 1 (.. i + 3) of an XCD are the slices of ONE tile: the same code stream, in step
         const uint32_t xcd = b & 7, i = b >> 3, sx = a.xcd_sx ? a.xcd_sx : 1u;
         slice = (xcd / a.xcd_group) * sx + i %% sx;
+        spos = i %% sx;
+        sxn = sx;
         ti = a.xcd_contig ? (xcd %% a.xcd_group) * a.xcd_contig + i / sx : (xcd %% a.xcd_group) + a.xcd_group * (i / sx);
     } else {
         slice = b %% a.nslices;
@@ -697,7 +711,7 @@ def main():
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "pygim_amd", "csrc", "lds_kernel_gen.hpp")
     if "--out" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1]
-    text = HEADER % dict(KA8=GEOS[8].KA, KA16=GEOS[16].KA, B8=GEOS[8].BATCH, B16=GEOS[16].BATCH, KAL=GEO_L16.KA, BL=GEO_L16.BATCH, KAC8=GEO_CODE8.KA)
+    text = HEADER % dict(KA8=GEOS[8].KA, KA16=GEOS[16].KA, B8=GEOS[8].BATCH, B16=GEOS[16].BATCH, KAL=GEO_L16.KA, BL=GEO_L16.BATCH, KAC8=GEO_CODE8.KA, VT8=VTOUCH8)
     variants = []
     for nw in (8, 16):
         variants.append((f"k_lds_spmm_f32_w{nw}", "v_add_f32", nw, 0, "FLT32, unit weights: sums in stored order, bit-identical to the CPU loop"))
@@ -748,6 +762,7 @@ def main():
             g = GEO_L16 if nw == "L16" else (GEO_W16 if op_mul else GEOS[nw])
         clob = ", ".join([f'"v{i}"' for i in range(g.T0, min(g.vmax, 256))] + [f'"s{i}"' for i in range(g.TOK0, 100)])
         is_code = "_code" in name
+        is_c8 = is_code and bool(g.regmap)
         out_kind = v[7] if len(v) > 7 else None
         cslice, fps = {None: (256, 64), "i8": (128, 128), "i8_deq": (512, 128), "i16_deq": (512, 128), "f64": (512, 64), "i64": (512, 64)}[out_kind]
         ts = name.endswith("_ts")
@@ -768,10 +783,12 @@ def main():
                               code_decl=("    const uint64_t code_a = (uint64_t)(a.code + a.code_start[(uint64_t)ti * NW + wave]);\n"
                                          "    const uint64_t code_s = ((uint64_t)((uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(code_a >> 32))) << 32) | "
                                          "(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)code_a);" if is_code else "") +
+                                        ("\n    const uint32_t tmul = __builtin_amdgcn_readfirstlane((a.touch_share && sxn > 1 && wave % sxn != spos) ? 0u : 16u);"
+                                         if is_c8 else "\n    (void)spos; (void)sxn;") +
                                         ("\n    const uint64_t stamps_a = (uint64_t)(a.stamps + ((uint64_t)b * NW + wave) * 4);\n"
                                          "    const uint64_t stamps_s = ((uint64_t)((uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(stamps_a >> 32))) << 32) | "
                                          "(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)stamps_a);" if ts else ""),
-                              code_ops=((',\n          [code] "s"(code_s), [hsplit] "s"(a.half_split)' if is_code else "") + (', [stamps] "s"(stamps_s)' if ts else "")),
+                              code_ops=((',\n          [code] "s"(code_s), [hsplit] "s"(a.half_split)' if is_code else "") + (', [tmul] "s"(tmul)' if is_c8 else "") + (', [stamps] "s"(stamps_s)' if ts else "")),
                               piece_expr=("a.piece_bytes" if is_code else "PIECE"))
         if guard:
             text += "#endif  // PYGIM_LDS_ABLATE\n"
