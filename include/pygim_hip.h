@@ -254,6 +254,14 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
  *   pygim_edge_softmax:  out[e, k] = exp(s[e, k] - m) / sum_{e' in row(e)} exp(s[e', k] - m), m the row's and head's maximum;
  *     scores and out: [nnz, heads] contiguous; the sum runs over the row's stored entries (duplicates are separate entries); stable
  *     for finite scores of any magnitude.
+ *     Non-finite scores (here and in pygim_gat_aggregate and pygim_sparse_attention below, whose scores are computed from a_src / K;
+ *     pygim_gatv2_aggregate has no masking input: x_src is score and value at once, so a non-finite x_src makes NaN the (row, head)s
+ *     that gather it, and only those): a score of -inf masks its entry --
+ *     its probability is exactly 0 and the softmax of the (row, head) runs over the rest, wherever the masked entries stand in the row;
+ *     heads are independent.  A (row, head) whose scores are ALL -inf is 0 / 0: NaN probabilities / NaN out over the head's features,
+ *     lse = -inf (torch.softmax, torch.logsumexp).  One +inf or NaN score makes its (row, head) NaN and nothing else.  Non-finite
+ *     features (X, V) stay in the outputs they are summed into: NaN and +-inf propagate as in a plain sum, nowhere else (a masked
+ *     entry's features are still multiplied by its probability 0, so they must be finite).
  *   pygim_edge_softmax_backward:  out[e, k] = P[e, k] * (dP[e, k] - sum_{e' in row(e)} P[e', k] * dP[e', k]).                          */
 int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads);
 int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *values,

@@ -33,6 +33,16 @@ __device__ inline float es_exp(float x) { return expf(x); }
 __device__ inline double es_exp(double x) { return exp(x); }
 template <typename T> __device__ inline T es_neg_inf() { return -__builtin_huge_val(); }
 template <> __device__ inline float es_neg_inf<float>() { return -__builtin_huge_valf(); }
+// what is subtracted from the scores under a maximum m: m itself, or 0 when every score so far is -inf (masked), so that such a score
+// gives exp(-inf - 0) = 0 and never exp(-inf - -inf) = NaN.  The partial of an all-masked stretch is then the neutral (-inf, 0).
+template <typename T> __device__ inline T es_shift(T m) { return m == es_neg_inf<T>() ? T(0) : m; }
+// where the running maximum of an online softmax starts (k_gat_gather and its siblings): the lowest FINITE number, not -inf.  No score
+// but -inf lies below it, so it changes no maximum; entries that are all -inf (masked) leave M there and give p = exp(-inf - M) = 0
+// instead of exp(-inf - -inf) = NaN, with no select in the scan.  (lowest, 0, 0) is neutral in gat_scales like (-inf, 0, 0): against a
+// larger maximum it scales by exp(lowest - M) = 0, against itself by exactly 1.  A (row, head) of nothing but -inf ends as (lowest, 0, 0):
+// out = 0 * (1 / 0) = NaN, lse = lowest + log(0) = -inf.
+template <typename T> __device__ inline T es_lowest() { return -__DBL_MAX__; }
+template <> __device__ inline float es_lowest<float>() { return -__FLT_MAX__; }
 
 inline uint64_t edge_softmax_batches(uint64_t nnz) { return (nnz + 63) / 64; }
 inline uint64_t edge_softmax_workspace_bytes(uint64_t nnz, uint64_t heads, size_t elem) {
@@ -148,7 +158,7 @@ __global__ __launch_bounds__(256) void k_es_batch(const uint32_t *__restrict__ r
                 } else {
                     if constexpr (MODE == ES_FORWARD) {
                         m = es_segment_total<T, true>(x[i], lane, q.ds, q.de);
-                        s = es_segment_total<T, false>(valid ? es_exp(x[i] - m) : T(0), lane, q.ds, q.de);
+                        s = es_segment_total<T, false>(valid ? es_exp(x[i] - es_shift(m)) : T(0), lane, q.ds, q.de);
                     } else {
                         s = es_segment_total<T, false>(x[i] * y[i], lane, q.ds, q.de);
                     }
@@ -157,7 +167,7 @@ __global__ __launch_bounds__(256) void k_es_batch(const uint32_t *__restrict__ r
                         slot[(k0 + i) * 2 + 1] = s;
                     }
                 }
-                if constexpr (MODE == ES_FORWARD) res[i] = es_exp(x[i] - m) / s;
+                if constexpr (MODE == ES_FORWARD) res[i] = es_exp(x[i] - es_shift(m)) / s;
                 else res[i] = x[i] * (y[i] - s);
             }
             if (valid && (FINISH ? across : !across)) {

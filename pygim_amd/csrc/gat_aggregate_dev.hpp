@@ -17,6 +17,8 @@
 //     p = exp(s - M), l += p, acc += p * x per entry, in entry order;
 //   * partial results (m, l, acc) meet by gat_merge -- es_merge carrying the accumulator: (-inf, 0, 0) is neutral, an equal maximum
 //     scales by exactly 1 -- in the xor tree of the lane groups, and in k_gat_fixup over the slots of the runs a row is cut across;
+//   * a row's m starts at es_lowest (the lowest finite number, neutral as well), so scores of -inf -- masked entries -- fold as p = 0
+//     wherever they stand, and a (row, head) of nothing else stores NaN and lse = -inf (edge_softmax_dev.hpp on es_lowest);
 //   * the workspace slots hold the raw (m, l, acc): h accumulators per slot as in k_row_gather, and behind them 2 numbers per head and
 //     slot; the division by l happens only where a finished row is stored.
 // No atomics, every order is fixed by the CSR: the same bits on every launch.
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
     const auto reset = [&]() {
 #pragma unroll
         for (int v = 0; v < NV; v++) {
-            m[v] = es_neg_inf<T>();
+            m[v] = es_lowest<T>();
             l[v] = T(0);
 #pragma unroll
             for (int i = 0; i < VEC; i++) acc[v][i] = T(0);
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
 #pragma unroll
                     for (int v = 0; v < NV; v++) {
                         x[u][v] = V(0);
-                        s[u][v] = es_neg_inf<T>();
+                        s[u][v] = es_lowest<T>();   // an entry slot that is not in flight: never above M
                         if (ok[u] && fok[v]) {
                             x[u][v] = *(const V *)(xr + f[v]);
                             s[u][v] = ar[hv[v]];

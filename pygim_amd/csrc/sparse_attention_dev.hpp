@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
     T acc[NP][VEC], m, l;
     const uint64_t slots = wave * 2 * (uint64_t)h;   // the run's two accumulator slots, in elements
     const auto reset = [&]() {
-        m = es_neg_inf<T>();
+        m = es_lowest<T>();
         l = T(0);
 #pragma unroll
         for (int p = 0; p < NP; p++)
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
                 T M = m;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    s[u] = ok[u] ? scale * s[u] : es_neg_inf<T>();
+                    s[u] = ok[u] ? scale * s[u] : es_lowest<T>();   // not in flight: never above M
                     M = s[u] > M ? s[u] : M;
                 }
                 const T c = m == M ? T(1) : es_exp(m - M);

@@ -16,6 +16,12 @@ from pygim_amd.backend_pim import spmm as spmm_mod
 from pygim_amd.sparse_tensor import SparseTensorShim
 
 
+def softmax_shift(m):
+    """what the kernels subtract from the scores under a maximum m: m, or 0 when every score is -inf (masked), so that a masked score
+    gives exp(-inf) = 0 and a fully masked row 0 / 0 = NaN with a log-sum-exp of -inf"""
+    return np.where(np.isneginf(m), 0.0, m)
+
+
 def _rows(ptr, rows, ld, width, npdt):
     """a [rows, width] window of a row-major buffer with row stride ld (elements)"""
     if rows == 0:
@@ -79,10 +85,11 @@ class FakeLibA(FakeLib):
         s = _view(s_ptr, nnz * heads, npdt).reshape(nnz, heads).astype(np.float64)
         m = np.full((nrows, heads), -np.inf)
         np.maximum.at(m, row, s)
-        e = np.exp(s - m[row])
+        e = np.exp(s - softmax_shift(m)[row])
         z = np.zeros((nrows, heads))
         np.add.at(z, row, e)
-        _view(out_ptr, nnz * heads, npdt).reshape(nnz, heads)[:] = (e / z[row]).astype(npdt)
+        with np.errstate(invalid="ignore"):   # a fully masked row: 0 / 0
+            _view(out_ptr, nnz * heads, npdt).reshape(nnz, heads)[:] = (e / z[row]).astype(npdt)
 
     def edge_softmax_backward(self, dtype, nrows, rowptr_ptr, nnz, p_ptr, dp_ptr, heads, out_ptr, ws_ptr, ws_bytes, stream=0):
         self.calls.append("edge_softmax_backward")

@@ -9,7 +9,7 @@ from fake_abi import NP_OF, _view
 from pygim_amd import gnn, pim_ops
 from pygim_amd.attention import gat_aggregate
 from pygim_amd.sparse_tensor import SparseTensorShim
-from test_attention_cpu import FakeLibA, _rows, gat_reference, graph_of, multigraph
+from test_attention_cpu import FakeLibA, _rows, gat_reference, graph_of, multigraph, softmax_shift
 from conftest import random_csr
 
 
@@ -39,12 +39,13 @@ class FakeLibG(FakeLibA):
             s = np.where(z >= 0, z, negative_slope * z)
             m = np.full((nrows, heads), -np.inf)
             np.maximum.at(m, row, s)
-            e = np.exp(s - m[row])
+            e = np.exp(s - softmax_shift(m)[row])
             l = np.zeros((nrows, heads))
             np.add.at(l, row, e)
-            np.add.at(acc, row, np.repeat(e / l[row], h // heads, axis=1) * X[col])
             full = np.diff(rowptr) > 0
-            lse[full] = m[full] + np.log(l[full])
+            with np.errstate(invalid="ignore", divide="ignore"):   # a fully masked row: 0 / 0 = NaN, lse = -inf + log(0) = -inf
+                np.add.at(acc, row, np.repeat(e / l[row], h // heads, axis=1) * X[col])
+                lse[full] = m[full] + np.log(l[full])
         out[:] = acc.astype(npdt)
         if lse_ptr:
             _view(lse_ptr, nrows * heads, npdt).reshape(nrows, heads)[:] = lse.astype(npdt)

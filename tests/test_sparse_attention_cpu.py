@@ -10,7 +10,7 @@ from fake_abi import NP_OF, PygimError, _view
 from pygim_amd import gnn, pim_ops
 from pygim_amd.attention import sparse_attention
 from pygim_amd.sparse_tensor import SparseTensorShim
-from test_attention_cpu import _rows, graph_of, multigraph
+from test_attention_cpu import _rows, graph_of, multigraph, softmax_shift
 from test_gat_fused_cpu import FakeLibG
 
 
@@ -44,12 +44,13 @@ class FakeLibS(FakeLibG):
             s = scale * np.einsum("ekf,ekf->ek", Q[row], K[col])
             m = np.full((nrows, heads), -np.inf)
             np.maximum.at(m, row, s)
-            e = np.exp(s - m[row])
+            e = np.exp(s - softmax_shift(m)[row])
             l = np.zeros((nrows, heads))
             np.add.at(l, row, e)
-            np.add.at(acc, row, np.repeat(e / l[row], hd, axis=1) * V[col])
             full = np.diff(rowptr) > 0
-            lse[full] = m[full] + np.log(l[full])
+            with np.errstate(invalid="ignore", divide="ignore"):   # a fully masked row: 0 / 0 = NaN, lse = -inf + log(0) = -inf
+                np.add.at(acc, row, np.repeat(e / l[row], hd, axis=1) * V[col])
+                lse[full] = m[full] + np.log(l[full])
         out[:] = acc.astype(npdt)
         if lse_ptr:
             _view(lse_ptr, nrows * heads, npdt).reshape(nrows, heads)[:] = lse.astype(npdt)
