@@ -395,6 +395,47 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
                                int64_t nnz, const void *values /* A's order, or NULL */, const void *G, int64_t ldg,
                                const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream);
 
+/* ---- which kernel instantiation and lane layout a call of the entry points above gets ----
+ * The decision their launchers take, from the host functions the launchers themselves call: no device is touched and nothing is
+ * launched (like the *_workspace functions it works without a GPU and without pygim_init_*).  `kind` names the entry point, `dtype`
+ * the storage type, `aligned` != 0 says that every row stride is a multiple of a 16-byte piece and every base pointer (the
+ * workspace included) a multiple of 16 bytes.  heads is ignored by SDDMM, SPMM_REDUCE and SPMM_REDUCE_BACKWARD, h by EDGE_SOFTMAX
+ * (forward and backward are one kind: the backward only has one more pointer that must be aligned).
+ *   out[0] vec       features per piece (per lane and load): 16 / element size, or 1
+ *   out[1] pieces    pieces a lane holds at once: 1 or 2 (row walkers: SPMM_VALUES, SPMM_REDUCE, GAT_AGGREGATE, SPMM_REDUCE_BACKWARD),
+ *                    1, 2 or 4 (head-wise: SPARSE_ATTENTION, GATV2_*), 1 .. 4 (SDDMM), 1 (EDGE_SOFTMAX)
+ *   out[2] LH        lanes across the features of one head (head-wise kernels); L for the others
+ *   out[3] L         lanes per entry (a power of two; 64 / L entries side by side in a wave)
+ *   out[4] per       heads per block, L / LH (head-wise kernels); 1 for the others
+ *   out[5] chunks    blockIdx.y chunks over all launches: of 128 pieces (row walkers), of `per` heads (head-wise); SDDMM: passes of 4
+ *                    pieces per lane; EDGE_SOFTMAX: steps over an entry's heads
+ *   out[6] launches  launches of the gather kernel (65535 chunks each at most; more than one only for the head-wise kernels)
+ *   out[7] flags     PYGIM_SHAPE_PART_PIECE  a lane's last piece exists only on some lanes (row walkers, SDDMM: pieces % L != 0;
+ *                                            head-wise: a head's pieces < out[1] * LH)
+ *                    PYGIM_SHAPE_PART_CHUNK  the last chunk (SDDMM: pass) holds fewer pieces, or fewer heads, than the others
+ *                    PYGIM_SHAPE_PART_HEADS  heads % per != 0: a block has lanes for heads that do not exist
+ *                    PYGIM_SHAPE_SCALAR_SIZE / _ALIGN  why vec == 1: the width (h, h / heads where a piece must not lie across two
+ *                                            heads, `heads` for EDGE_SOFTMAX) does not fill whole pieces / `aligned` is 0
+ * Returns PYGIM_ERR_INVALID for what the entry point itself rejects for these numbers: an unknown kind, a type it does not take,
+ * heads not dividing h, h / heads > 256 (head-wise), and h > 65535 * 128 for the row walkers -- one launch holds 65535 chunks, so
+ * pygim_spmm_values, pygim_spmm_reduce, pygim_gat_aggregate, their *_workspace functions (-1) and pygim_spmm_reduce_backward
+ * reject a wider row before any launch, whatever the alignment.                                                               */
+#define PYGIM_SHAPE_SPMM_VALUES 0
+#define PYGIM_SHAPE_SPMM_REDUCE 1
+#define PYGIM_SHAPE_GAT_AGGREGATE 2
+#define PYGIM_SHAPE_SPARSE_ATTENTION 3
+#define PYGIM_SHAPE_GATV2_AGGREGATE 4
+#define PYGIM_SHAPE_GATV2_BACKWARD 5
+#define PYGIM_SHAPE_SDDMM 6
+#define PYGIM_SHAPE_EDGE_SOFTMAX 7
+#define PYGIM_SHAPE_SPMM_REDUCE_BACKWARD 8
+#define PYGIM_SHAPE_PART_PIECE 1
+#define PYGIM_SHAPE_PART_CHUNK 2
+#define PYGIM_SHAPE_PART_HEADS 4
+#define PYGIM_SHAPE_SCALAR_SIZE 8
+#define PYGIM_SHAPE_SCALAR_ALIGN 16
+int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int aligned, int64_t out[8]);
+
 /* ---- introspection -----------------------------------------------------------
  * Milliseconds of the last host-pointer run, in the reference's Timer buckets
  * (support/timer.h; printed as [DATA] lines, spmm_mul_csr.c:563-580):

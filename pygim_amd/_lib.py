@@ -24,7 +24,7 @@ EXPORTS = [
     "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_edge_softmax", "pygim_edge_softmax_workspace", "pygim_edge_softmax_backward",
     "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
     "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace",
-    "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward",
+    "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward", "pygim_gather_launch_shape",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -32,6 +32,12 @@ INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
 FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention, gatv2_* and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
+# pygim_gather_launch_shape: the kinds, the names of out[0..7] and the bits of "flags"
+(SHAPE_SPMM_VALUES, SHAPE_SPMM_REDUCE, SHAPE_GAT_AGGREGATE, SHAPE_SPARSE_ATTENTION, SHAPE_GATV2_AGGREGATE, SHAPE_GATV2_BACKWARD, SHAPE_SDDMM,
+ SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD) = range(9)
+SHAPE_FIELDS = ("vec", "pieces", "LH", "L", "per", "chunks", "launches", "flags")
+SHAPE_PART_PIECE, SHAPE_PART_CHUNK, SHAPE_PART_HEADS, SHAPE_SCALAR_SIZE, SHAPE_SCALAR_ALIGN = 1, 2, 4, 8, 16
+GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, gat_aggregate and spmm_reduce_backward
 
 
 class PygimError(RuntimeError):
@@ -92,6 +98,7 @@ def lib():
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
         L.pygim_spmm_reduce_backward.argtypes = [c_int, c_i64, vp, vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp]
+        L.pygim_gather_launch_shape.argtypes = [c_int, c_int, c_i64, c_i64, c_int, p_i64]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -335,6 +342,15 @@ def spmm_reduce_backward(dtype, ncols, rowptr_t_ptr, rows_t_ptr, perm_ptr, nnz, 
     """dX[c] = sum over the entries of row c of A^T of (arg[r] == e ? values[e] * G[r] : 0): the gradient of max / min (FLT32 / DBL64)"""
     check(lib().pygim_spmm_reduce_backward(int(dtype), int(ncols), _vp(rowptr_t_ptr), _vp(rows_t_ptr), _vp(perm_ptr), int(nnz), _vp(val_ptr),
                                            _vp(g_ptr), int(ldg), _vp(arg_ptr), int(h), _vp(dx_ptr), int(ldd), _vp(stream)))
+
+
+def gather_launch_shape(kind, dtype, h, heads=1, aligned=True):
+    """the kernel instantiation and lane layout the entry point `kind` (SHAPE_*) launches for these numbers, as a dict over SHAPE_FIELDS
+    (include/pygim_hip.h); no device is needed.  PygimError for numbers the entry point rejects"""
+    out = (ctypes.c_int64 * 8)()
+    if lib().pygim_gather_launch_shape(int(kind), int(dtype), int(h), int(heads), 1 if aligned else 0, out) != 0:
+        raise PygimError(ERR_INVALID, f"no launch shape for kind {kind}, type {dtype}, h {h}, heads {heads}")
+    return dict(zip(SHAPE_FIELDS, [int(v) for v in out]))
 
 
 def group_free(handle):

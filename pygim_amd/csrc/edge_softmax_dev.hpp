@@ -225,6 +225,14 @@ __global__ __launch_bounds__(256) void k_es_combine(uint64_t nbatches, uint32_t 
     }
 }
 
+// k_es_batch: a lane per entry, the entry's heads in steps of a 16-byte piece when `heads` fills whole pieces (every entry's heads then
+// start 16-byte aligned when the arrays do) and a, b and out are aligned; else one head per step
+inline LaunchShape edge_softmax_shape(uint32_t heads, uint32_t V, bool aligned) {
+    LaunchShape g = launch_shape_piece(heads, V, aligned);
+    g.chunks = heads / g.vec;   // steps of the loop over the heads
+    return g;
+}
+
 template <typename T, int MODE>
 inline void launch_edge_softmax(const uint32_t *rowptr, uint32_t nrows, uint32_t nnz, const T *a, const T *b, uint32_t heads, T *out, void *workspace,
                                 hipStream_t st) {
@@ -233,7 +241,7 @@ inline void launch_edge_softmax(const uint32_t *rowptr, uint32_t nrows, uint32_t
     T *ws = (T *)workspace;
     uint32_t *tail_end = (uint32_t *)((char *)workspace + (nb * 4 * heads * sizeof(T) + 15) / 16 * 16);
     const unsigned blocks = (unsigned)((((uint64_t)nnz + ES_EPW - 1) / ES_EPW + 3) / 4);
-    const bool vec = heads % V == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (MODE == ES_FORWARD || (uintptr_t)b % 16 == 0);
+    const bool vec = edge_softmax_shape(heads, V, (uintptr_t)a % 16 == 0 && (uintptr_t)out % 16 == 0 && (MODE == ES_FORWARD || (uintptr_t)b % 16 == 0)).vec > 1;
     if (vec) hipLaunchKernelGGL((k_es_batch<T, (int)V, MODE, false>), dim3(blocks), dim3(256), 0, st, rowptr, nrows, nnz, a, b, heads, out, ws, tail_end);
     else hipLaunchKernelGGL((k_es_batch<T, 1, MODE, false>), dim3(blocks), dim3(256), 0, st, rowptr, nrows, nnz, a, b, heads, out, ws, tail_end);
     if (nb <= 1) return;

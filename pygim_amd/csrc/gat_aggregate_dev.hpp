@@ -254,19 +254,17 @@ __global__ __launch_bounds__(256) void k_gat_empty(const uint32_t *__restrict__ 
 
 template <typename T, typename S, int VEC>
 inline void launch_gat_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
-                                T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, hipStream_t st) {
+                                T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, const LaunchShape &g,
+                                hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    const uint32_t pieces = (h + VEC - 1) / VEC;
-    if (pieces <= 32) {
-        uint32_t L = 1;
-        while (L < pieces) L <<= 1;
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, L,
+    if (g.L < 64) {
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, g.L,
                            out, ldo, lse, ws, ws_stat);
-    } else if (pieces <= 64) {
+    } else if (g.npl == 1) {
         hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, true>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
                            out, ldo, lse, ws, ws_stat);
     } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
                            slope, X, ldx, h, 64u, out, ldo, lse, ws, ws_stat);
     }
 }
@@ -280,9 +278,10 @@ inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind,
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
-    const bool vec = (h / heads) % V == 0 && ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_gat_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
-    else launch_gat_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, st);
+    const bool aligned = ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
+    const LaunchShape g = row_gather_shape(h, h / heads, V, aligned);   // the walker's layout
+    if (g.vec > 1) launch_gat_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, st);
+    else launch_gat_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

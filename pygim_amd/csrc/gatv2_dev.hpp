@@ -423,38 +423,22 @@ __global__ __launch_bounds__(256) void k_gatv2_datt_reduce(const T *__restrict__
     dst[(uint64_t)blockIdx.y * h + f] = s;
 }
 
-// the lane layout of launch_sa_gather_v: NP pieces per lane (1 up to 64 pieces per head, then 2, then 4), LH lanes per head, L lanes per entry
-struct Gv2Shape {
-    uint32_t np, LH, L, per, chunks;
-};
-inline Gv2Shape gatv2_shape(uint32_t h, uint32_t heads, uint32_t vec) {
-    Gv2Shape g;
-    const uint32_t pieces = (h / heads + vec - 1) / vec;
-    g.np = pieces <= 64 ? 1 : pieces <= 128 ? 2 : 4;
-    g.LH = 1;
-    while (g.LH * g.np < pieces) g.LH <<= 1;
-    for (g.L = g.LH; g.L < 64 && g.L < (uint64_t)heads * g.LH; g.L <<= 1) {}
-    g.per = g.L / g.LH;                         // heads per block
-    g.chunks = (heads + g.per - 1) / g.per;     // blockIdx.y; a launch takes at most 65535 of them
-    return g;
-}
-
+// the lane layout is head_gather_shape's (sparse_attention_dev.hpp)
 template <typename T, typename S, int VEC>
 inline void launch_gatv2_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Xd, uint64_t ldxd, const S *Xs,
                                   uint64_t ldxs, const T *att, uint32_t h, uint32_t heads, T slope, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat,
-                                  hipStream_t st) {
+                                  const LaunchShape &g, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    const Gv2Shape g = gatv2_shape(h, heads, VEC);
 #define PYGIM_GV2_LAUNCH(NP)                                                                                                                          \
-    for (uint32_t c0 = 0; c0 < g.chunks; c0 += 65535u)                                                                                                \
-    hipLaunchKernelGGL((k_gatv2_gather<T, S, VEC, NP>), dim3(blocks, g.chunks - c0 < 65535u ? g.chunks - c0 : 65535u), dim3(256), 0, st, rowptr, colind, \
-                       nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, c0 * g.per, slope, g.LH, g.L, out, ldo, lse, ws, ws_stat)
+    for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                         \
+    hipLaunchKernelGGL((k_gatv2_gather<T, S, VEC, NP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
+                       rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, c0 * g.per, slope, g.LH, g.L, out, ldo, lse, ws, ws_stat)
     constexpr uint32_t MAX_NP = (GV2_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);   // only the piece counts a head of GV2_MAX_HEAD can need
-    if (g.np == 1) PYGIM_GV2_LAUNCH(1);
+    if (g.npl == 1) PYGIM_GV2_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
-        if (g.np == 2) PYGIM_GV2_LAUNCH(2);
+        if (g.npl == 2) PYGIM_GV2_LAUNCH(2);
     if constexpr (MAX_NP >= 4)
-        if (g.np == 4) PYGIM_GV2_LAUNCH(4);
+        if (g.npl == 4) PYGIM_GV2_LAUNCH(4);
 #undef PYGIM_GV2_LAUNCH
 }
 
@@ -469,10 +453,11 @@ inline void launch_gatv2_aggregate(const uint32_t *rowptr, const uint32_t *colin
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
-    const bool vec = (h / heads) % V == 0 && ldxd % V == 0 && ldxs % V == 0 && ldo % V == 0 && (uintptr_t)Xd % 16 == 0 && (uintptr_t)Xs % 16 == 0 &&
-                     (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_gatv2_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, st);
-    else launch_gatv2_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, st);
+    const bool aligned = ldxd % V == 0 && ldxs % V == 0 && ldo % V == 0 && (uintptr_t)Xd % 16 == 0 && (uintptr_t)Xs % 16 == 0 &&
+                         (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
+    const LaunchShape g = head_gather_shape(h, heads, V, aligned);
+    if (g.vec > 1) launch_gatv2_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, st);
+    else launch_gatv2_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);
@@ -491,19 +476,19 @@ inline uint64_t gatv2_backward_workspace_bytes(uint64_t nnz, uint64_t h, size_t 
 template <typename T, typename S, int VEC, bool TRANSPOSED>
 inline void launch_gatv2_grad_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *own, uint64_t ld_own, const S *oth,
                                 uint64_t ld_oth, const T *att, uint32_t h, uint32_t heads, T slope, const S *G, uint64_t ldg, const T *lse, const T *delta,
-                                S *d_own, uint64_t ldd, T *ws, T *ws_datt, hipStream_t st) {
+                                S *d_own, uint64_t ldd, T *ws, T *ws_datt, const LaunchShape &g, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    const Gv2Shape g = gatv2_shape(h, heads, VEC);
 #define PYGIM_GV2_LAUNCH(NP)                                                                                                                           \
-    for (uint32_t c0 = 0; c0 < g.chunks; c0 += 65535u)                                                                                                 \
-    hipLaunchKernelGGL((k_gatv2_grad<T, S, VEC, NP, TRANSPOSED>), dim3(blocks, g.chunks - c0 < 65535u ? g.chunks - c0 : 65535u), dim3(256), 0, st, rowptr, \
-                       colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, c0 * g.per, slope, G, ldg, lse, delta, g.LH, g.L, d_own, ldd, ws, ws_datt)
+    for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                          \
+    hipLaunchKernelGGL((k_gatv2_grad<T, S, VEC, NP, TRANSPOSED>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
+                       rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, c0 * g.per, slope, G, ldg, lse, delta, g.LH, g.L, d_own, ldd, ws,   \
+                       ws_datt)
     constexpr uint32_t MAX_NP = (GV2_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);
-    if (g.np == 1) PYGIM_GV2_LAUNCH(1);
+    if (g.npl == 1) PYGIM_GV2_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
-        if (g.np == 2) PYGIM_GV2_LAUNCH(2);
+        if (g.npl == 2) PYGIM_GV2_LAUNCH(2);
     if constexpr (MAX_NP >= 4)
-        if (g.np == 4) PYGIM_GV2_LAUNCH(4);
+        if (g.npl == 4) PYGIM_GV2_LAUNCH(4);
 #undef PYGIM_GV2_LAUNCH
 }
 
@@ -519,14 +504,15 @@ inline void launch_gatv2_backward(const uint32_t *rowptr, const uint32_t *colind
     T *part = (T *)((char *)workspace + gatv2_datt_offset(nnz, h, sizeof(T)));
     T *part2 = (T *)((char *)workspace + gatv2_datt2_offset(nnz, h, sizeof(T)));
     if (nnz > 0) {
-        const bool vec = (h / heads) % V == 0 && ld_own % V == 0 && ld_oth % V == 0 && ldg % V == 0 && ldd % V == 0 && (uintptr_t)own % 16 == 0 &&
-                         (uintptr_t)oth % 16 == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)d_own % 16 == 0 && (uintptr_t)ws % 16 == 0;
-        if (vec)
+        const bool aligned = ld_own % V == 0 && ld_oth % V == 0 && ldg % V == 0 && ldd % V == 0 && (uintptr_t)own % 16 == 0 && (uintptr_t)oth % 16 == 0 &&
+                             (uintptr_t)G % 16 == 0 && (uintptr_t)d_own % 16 == 0 && (uintptr_t)ws % 16 == 0;
+        const LaunchShape g = head_gather_shape(h, heads, V, aligned);
+        if (g.vec > 1)
             launch_gatv2_grad_v<T, S, (int)V, TRANSPOSED>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta, d_own,
-                                                          ldd, ws, part, st);
+                                                          ldd, ws, part, g, st);
         else
             launch_gatv2_grad_v<T, S, 1, TRANSPOSED>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta, d_own, ldd, ws,
-                                                     part, st);
+                                                     part, g, st);
         if (runs > 1)
             hipLaunchKernelGGL((k_row_gather_fixup<T, S, FoldSum<false>>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, ws, nullptr,
                                d_own, ldd, nullptr);

@@ -678,7 +678,7 @@ int pygim_sddmm(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *
 int64_t pygim_spmm_values_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
     (void)heads;
-    if (!is_gather_type(dtype) || nnz < 0 || h < 1) return -1;
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || h > (int64_t)RG_MAX_H) return -1;
     return (int64_t)row_gather_slot_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
 }
 
@@ -693,7 +693,7 @@ int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_values: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "spmm_values: heads must divide h");
-    if (int rc = check_csr_call("spmm_values", "rowptr / colind / values / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+    if (int rc = check_csr_call("spmm_values", "rowptr / colind / values / X / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {colind, nnz > 0}, {values, nnz > 0}, {X, nnz > 0}},
                                 pygim_spmm_values_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
@@ -710,7 +710,7 @@ int pygim_spmm_values(int dtype, int64_t nrows, const int32_t *rowptr, const int
 
 int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
-    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0) return -1;
+    if (!is_gather_type(dtype) || nnz < 0 || h < 1 || h > (int64_t)RG_MAX_H || heads < 1 || h % heads != 0) return -1;
     return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
 }
 
@@ -720,7 +720,7 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: heads must divide h");
-    if (int rc = check_csr_call("gat_aggregate", "rowptr / colind / a_dst / a_src / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+    if (int rc = check_csr_call("gat_aggregate", "rowptr / colind / a_dst / a_src / X / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {a_dst, nnz > 0}, {a_src, nnz > 0}, {X, nnz > 0}},
                                 pygim_gat_aggregate_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
@@ -871,7 +871,7 @@ int pygim_edge_softmax_backward(int dtype, int64_t nrows, const int32_t *rowptr,
 int64_t pygim_spmm_reduce_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
     if (op != PYGIM_REDUCE_MEAN && op != PYGIM_REDUCE_MAX && op != PYGIM_REDUCE_MIN) return -1;
     if (op == PYGIM_REDUCE_MEAN ? !is_gather_type(dtype) : dtype_size(dtype) == 0) return -1;   // 16-bit features: the mean only
-    if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > 0x7FFFFFFFll) return -1;
+    if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
     return (int64_t)spmm_reduce_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
 }
 
@@ -885,7 +885,7 @@ int pygim_spmm_reduce(int dtype, int op, int64_t nrows, const int32_t *rowptr, c
     if (op != PYGIM_REDUCE_MEAN && is_half_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce: max / min take no 16-bit type (FLT16 / BF16: mean only)");
     if (op == PYGIM_REDUCE_MEAN && arg) return fail(PYGIM_ERR_INVALID, "spmm_reduce: mean has no arg output");
     if (arg && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce: arg must be 4-byte aligned");
-    if (int rc = check_csr_call("spmm_reduce", "rowptr / colind / X / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldx, ldo,
+    if (int rc = check_csr_call("spmm_reduce", "rowptr / colind / X / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
                                 {{rowptr, true}, {out, nrows > 0}, {arg, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {values, nnz > 0, true}},
                                 pygim_spmm_reduce_workspace(dtype, op, nrows, nnz, h), workspace, workspace_bytes))
         return rc;
@@ -913,7 +913,7 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
                                const void *values, const void *G, int64_t ldg, const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream) {
     if (int rc = need_init()) return rc;
     if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: type must be FLT32 or DBL64");
-    if (int rc = check_csr_call("spmm_reduce_backward", "rowptr_t / rows_t / perm / G / arg / dX", ncols, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldg, ldd,
+    if (int rc = check_csr_call("spmm_reduce_backward", "rowptr_t / rows_t / perm / G / arg / dX", ncols, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldg, ldd,
                                 {{rowptr_t, true}, {dX, ncols > 0}, {rows_t, nnz > 0}, {perm, nnz > 0}, {G, nnz > 0}, {arg, nnz > 0}, {values, nnz > 0, true}}))
         return rc;
     if (nnz > 0 && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_reduce_backward: arg must be 4-byte aligned");
@@ -923,6 +923,36 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
                                   arg, (uint32_t)h, (T *)dX, (uint64_t)ldd, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the launch shape of a gather entry point, from the functions its launcher calls; no device, no launch (like the *_workspace functions)
+int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int aligned, int64_t out[8]) {
+    static_assert(LS_PART_PIECE == PYGIM_SHAPE_PART_PIECE && LS_PART_CHUNK == PYGIM_SHAPE_PART_CHUNK && LS_PART_HEADS == PYGIM_SHAPE_PART_HEADS &&
+                      LS_SCALAR_SIZE == PYGIM_SHAPE_SCALAR_SIZE && LS_SCALAR_ALIGN == PYGIM_SHAPE_SCALAR_ALIGN,
+                  "the flags of include/pygim_hip.h");
+    if (!out) return PYGIM_ERR_INVALID;
+    const bool head_wise = kind == PYGIM_SHAPE_SPARSE_ATTENTION || kind == PYGIM_SHAPE_GATV2_AGGREGATE || kind == PYGIM_SHAPE_GATV2_BACKWARD;
+    const bool walker = kind == PYGIM_SHAPE_SPMM_VALUES || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_GAT_AGGREGATE ||
+                        kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD;
+    bool type_ok;
+    if (kind == PYGIM_SHAPE_SPMM_REDUCE) type_ok = dtype_size(dtype) != 0 || is_half_type(dtype);   // integers: max / min; 16-bit: the mean
+    else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) type_ok = is_float_type(dtype);
+    else type_ok = is_gather_type(dtype);
+    if (!(head_wise || walker || kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_EDGE_SOFTMAX) || !type_ok) return PYGIM_ERR_INVALID;
+    if (kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) heads = 1;   // they have none
+    if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) h = heads;                                                                           // it has no h
+    if (h < 1 || heads < 1 || heads > 0x7FFFFFFFll || h % heads != 0 || h > (walker ? (int64_t)RG_MAX_H : 0xFFFFFFFFll)) return PYGIM_ERR_INVALID;
+    if (head_wise && h / heads > (int64_t)SA_MAX_HEAD) return PYGIM_ERR_INVALID;
+    const uint32_t V = (uint32_t)(16 / gather_storage_size(dtype));
+    LaunchShape g;
+    if (head_wise) g = head_gather_shape((uint32_t)h, (uint32_t)heads, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SDDMM) g = sddmm_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) g = edge_softmax_shape((uint32_t)heads, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) g = spmm_reduce_bwd_shape((uint32_t)h, V, aligned != 0);
+    else g = row_gather_shape((uint32_t)h, (uint32_t)(h / heads), V, aligned != 0);
+    const int64_t v[8] = {g.vec, g.npl, g.LH, g.L, g.per, g.chunks, g.launches, g.flags};
+    for (int i = 0; i < 8; i++) out[i] = v[i];
     return 0;
 }
 

@@ -327,21 +327,43 @@ inline uint64_t row_gather_runs(uint64_t nnz) { return (nnz + RG_EPW - 1) / RG_E
 inline uint64_t row_gather_slot_bytes(uint64_t nnz, uint64_t h, size_t elem) { return row_gather_runs(nnz) * 2 * h * elem; }
 inline uint64_t row_gather_index_offset(uint64_t nnz, uint64_t h, size_t elem) { return (row_gather_slot_bytes(nnz, h, elem) + 15) / 16 * 16; }
 
+// One launch holds LS_MAX_CHUNKS chunks of 128 pieces: the widest row k_row_gather, k_gat_gather and k_spmm_reduce_bwd take on their
+// one-element path.  The entry points (and their *_workspace functions) reject a wider h before any launch, whatever the alignment.
+constexpr uint64_t RG_MAX_H = (uint64_t)LS_MAX_CHUNKS * 128;
+
+// the lane layout of k_row_gather, k_gat_gather and k_spmm_reduce_bwd: up to `split` pieces a row is taken by L lanes side by side (a
+// power of two; 64 / L entries per wave-instruction), up to 64 by the whole wave, beyond that by two pieces per lane and blockIdx.y chunks
+// of 128 pieces.  width: what must fill whole pieces (h / heads: no piece lies across two heads).  h <= RG_MAX_H (the caller has checked).
+inline LaunchShape row_gather_shape(uint32_t h, uint32_t width, uint32_t V, bool aligned, uint32_t split = 32) {
+    LaunchShape g = launch_shape_piece(width, V, aligned);
+    const uint32_t pieces = (h + g.vec - 1) / g.vec;
+    if (pieces <= split) {
+        while (g.L < pieces) g.L <<= 1;
+    } else {
+        g.L = 64;
+        if (pieces > 64) {
+            g.npl = 2;
+            g.chunks = (pieces + 127) / 128;
+        }
+    }
+    g.LH = g.L;
+    if (pieces % g.L != 0) g.flags |= LS_PART_PIECE;
+    if (g.chunks > 1 && pieces % 128 != 0) g.flags |= LS_PART_CHUNK;
+    return g;
+}
+
 template <typename T, typename S, int VEC, typename Fold>
 inline void launch_row_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const S *X,
-                                uint64_t ldx, uint32_t h, S *out, uint64_t ldo, int32_t *arg, T *ws, int32_t *ws_idx, hipStream_t st) {
+                                uint64_t ldx, uint32_t h, S *out, uint64_t ldo, int32_t *arg, T *ws, int32_t *ws_idx, const LaunchShape &g, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    const uint32_t pieces = (h + VEC - 1) / VEC;
-    if (pieces <= 32) {
-        uint32_t L = 1;
-        while (L < pieces) L <<= 1;
-        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, false, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, L, out,
+    if (g.L < 64) {
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, false, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, g.L, out,
                            ldo, arg, ws, ws_idx);
-    } else if (pieces <= 64) {
+    } else if (g.npl == 1) {
         hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, true, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, 64u, out,
                            ldo, arg, ws, ws_idx);
     } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 2, true, Fold>), dim3(blocks, (pieces + 127) / 128), dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 2, true, Fold>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
                            heads, X, ldx, h, 64u, out, ldo, arg, ws, ws_idx);
     }
 }
@@ -357,9 +379,10 @@ inline void launch_row_gather(const uint32_t *rowptr, const uint32_t *colind, ui
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     int32_t *ws_idx = Fold::INDEXED ? (int32_t *)((char *)workspace + row_gather_index_offset(nnz, h, sizeof(T))) : nullptr;
-    const bool vec = (h / heads) % V == 0 && ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_row_gather_v<T, S, (int)V, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
-    else launch_row_gather_v<T, S, 1, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, st);
+    const bool aligned = ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
+    const LaunchShape g = row_gather_shape(h, h / heads, V, aligned);
+    if (g.vec > 1) launch_row_gather_v<T, S, (int)V, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, g, st);
+    else launch_row_gather_v<T, S, 1, Fold>(rowptr, colind, nrows, nnz, values, heads, X, ldx, h, out, ldo, arg, ws, ws_idx, g, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_row_gather_fixup<T, S, Fold>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, ws, ws_idx, out, ldo, arg);

@@ -21,6 +21,50 @@ namespace pygim {
 
 constexpr uint32_t SD_EPW = 256;   // entries per wave (4 batches of 64)
 
+// What a launch_* function of the gather family decides, as numbers: computed by the pure host functions *_shape() from the sizes, the
+// pieces a 16-byte load holds (V = 16 / sizeof(storage type)) and ONE alignment fact (`aligned`: every stride is a multiple of V and
+// every base pointer a multiple of 16 bytes).  The launchers launch what these functions say; pygim_gather_launch_shape
+// (include/pygim_hip.h) returns the same numbers without a device.
+struct LaunchShape {
+    uint32_t vec;        // features per piece: V, or 1
+    uint32_t npl;        // pieces a lane holds at once (NV of the row walkers, NP of the head-wise kernels, up to NVC of k_sddmm, 1 else)
+    uint32_t LH;         // lanes across one head's features (head-wise kernels); L elsewhere
+    uint32_t L;          // lanes per entry: 64 / L entries side by side in a wave
+    uint32_t per;        // heads per block (head-wise kernels); 1 elsewhere
+    uint32_t chunks;     // blockIdx.y chunks over all launches (k_sddmm: passes of NVC pieces; k_es_batch: steps over the heads)
+    uint32_t launches;   // launches of the gather kernel (65535 chunks each at most)
+    uint32_t flags;      // LS_* below
+};
+constexpr uint32_t LS_PART_PIECE = 1;    // the last piece of a lane exists only on some of the lanes (pieces % lanes != 0)
+constexpr uint32_t LS_PART_CHUNK = 2;    // the last chunk (pass) holds fewer pieces, or fewer heads, than the others
+constexpr uint32_t LS_PART_HEADS = 4;    // a block has lanes for more heads than it is given (heads % per != 0)
+constexpr uint32_t LS_SCALAR_SIZE = 8;   // vec == 1 because the width (a head's, or `heads` of edge_softmax) does not fill whole pieces
+constexpr uint32_t LS_SCALAR_ALIGN = 16; // vec == 1 because of `aligned` alone
+constexpr uint32_t LS_MAX_CHUNKS = 65535;   // gridDim.y
+
+// the piece: V features when `width` fills whole pieces and everything is aligned; else 1, with the reason in flags
+inline LaunchShape launch_shape_piece(uint32_t width, uint32_t V, bool aligned) {
+    LaunchShape g = {1u, 1u, 1u, 1u, 1u, 1u, 1u, 0u};
+    if (width % V != 0) g.flags = LS_SCALAR_SIZE;
+    else if (!aligned) g.flags = LS_SCALAR_ALIGN;
+    else g.vec = V;
+    return g;
+}
+
+// k_sddmm: L lanes cover the row's pieces (a power of two, at most 64), a lane holds up to 4 pieces at once and takes longer rows in passes
+inline LaunchShape sddmm_shape(uint32_t h, uint32_t V, bool aligned) {
+    LaunchShape g = launch_shape_piece(h, V, aligned);
+    const uint32_t pieces = (h + g.vec - 1) / g.vec;
+    while (g.L < 64 && g.L < pieces) g.L <<= 1;
+    g.LH = g.L;
+    const uint32_t nv = (pieces + g.L - 1) / g.L;   // pieces per lane and entry
+    g.npl = nv < 4 ? nv : 4;
+    g.chunks = (nv + 3) / 4;
+    if (pieces % g.L != 0) g.flags |= LS_PART_PIECE;
+    if (g.chunks > 1 && nv % 4 != 0) g.flags |= LS_PART_CHUNK;
+    return g;
+}
+
 // the last row r < nrows with rowptr[r] <= e, searched in [lo, nrows)
 __device__ inline uint32_t sd_row_of(const uint32_t *__restrict__ rowptr, uint32_t lo, uint32_t nrows, uint32_t e) {
     uint32_t hi = nrows;
@@ -135,14 +179,13 @@ inline void launch_sddmm_l(const uint32_t *rowptr, const uint32_t *colind, uint3
 
 template <typename T, typename S, int VEC>
 inline void launch_sddmm_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *G, uint64_t ldg, const S *X, uint64_t ldx,
-                           uint32_t h, T *out, hipStream_t st) {
-    const uint32_t pieces = (h + VEC - 1) / VEC;
-    if (pieces <= 1) launch_sddmm_l<T, S, VEC, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 2) launch_sddmm_l<T, S, VEC, 2>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 4) launch_sddmm_l<T, S, VEC, 4>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 8) launch_sddmm_l<T, S, VEC, 8>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 16) launch_sddmm_l<T, S, VEC, 16>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else if (pieces <= 32) launch_sddmm_l<T, S, VEC, 32>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+                           uint32_t h, T *out, uint32_t L, hipStream_t st) {
+    if (L == 1) launch_sddmm_l<T, S, VEC, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (L == 2) launch_sddmm_l<T, S, VEC, 2>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (L == 4) launch_sddmm_l<T, S, VEC, 4>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (L == 8) launch_sddmm_l<T, S, VEC, 8>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (L == 16) launch_sddmm_l<T, S, VEC, 16>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    else if (L == 32) launch_sddmm_l<T, S, VEC, 32>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
     else launch_sddmm_l<T, S, VEC, 64>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
 }
 
@@ -151,9 +194,10 @@ template <typename T, typename S = T>
 inline void launch_sddmm(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *G, uint64_t ldg, const S *X, uint64_t ldx,
                          uint32_t h, T *out, hipStream_t st) {
     constexpr uint32_t V = 16 / sizeof(S);
-    const bool vec = h % V == 0 && ldg % V == 0 && ldx % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)X % 16 == 0;
-    if (vec) launch_sddmm_v<T, S, (int)V>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
-    else launch_sddmm_v<T, S, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, st);
+    const bool aligned = ldg % V == 0 && ldx % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)X % 16 == 0;
+    const LaunchShape g = sddmm_shape(h, V, aligned);
+    if (g.vec > 1) launch_sddmm_v<T, S, (int)V>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, g.L, st);
+    else launch_sddmm_v<T, S, 1>(rowptr, colind, nrows, nnz, G, ldg, X, ldx, h, out, g.L, st);
 }
 
 }  // namespace pygim

@@ -203,28 +203,38 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
     if (pending) flush(true, head_open ? 0u : 1u, 0u);   // the run's last row goes on in the next run
 }
 
-// NP pieces per lane: 1 up to 64 pieces per head, then 2, then 4 (hd <= SA_MAX_HEAD: at most 256 scalar pieces)
+// the lane layout of the head-wise kernels (k_sa_gather, k_gatv2_gather, k_gatv2_grad): NP pieces per lane (1 up to 64 pieces per head, then
+// 2, then 4; hd <= SA_MAX_HEAD: at most 256 scalar pieces), LH lanes per head, L lanes per entry, L / LH heads per block and the rest of
+// the heads over blockIdx.y, LS_MAX_CHUNKS chunks per launch
+inline LaunchShape head_gather_shape(uint32_t h, uint32_t heads, uint32_t V, bool aligned) {
+    LaunchShape g = launch_shape_piece(h / heads, V, aligned);
+    const uint32_t pieces = (h / heads + g.vec - 1) / g.vec;
+    g.npl = pieces <= 64 ? 1 : pieces <= 128 ? 2 : 4;
+    while (g.LH * g.npl < pieces) g.LH <<= 1;
+    for (g.L = g.LH; g.L < 64 && g.L < (uint64_t)heads * g.LH; g.L <<= 1) {}
+    g.per = g.L / g.LH;                         // heads per block
+    g.chunks = (heads + g.per - 1) / g.per;     // blockIdx.y; a launch takes at most LS_MAX_CHUNKS of them
+    g.launches = (g.chunks + LS_MAX_CHUNKS - 1) / LS_MAX_CHUNKS;
+    if (pieces != g.npl * g.LH) g.flags |= LS_PART_PIECE;   // some (lane, piece) places of a head hold no feature
+    if (heads % g.per != 0) g.flags |= LS_PART_HEADS | (g.chunks > 1 ? LS_PART_CHUNK : 0u);
+    return g;
+}
+
 template <typename T, typename S, int VEC>
 inline void launch_sa_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Q, uint64_t ldq, const S *K, uint64_t ldk,
-                               const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, hipStream_t st) {
+                               const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat,
+                               const LaunchShape &g, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    const uint32_t pieces = (h / heads + VEC - 1) / VEC;
-    const uint32_t np = pieces <= 64 ? 1 : pieces <= 128 ? 2 : 4;
-    uint32_t LH = 1, L;
-    while (LH * np < pieces) LH <<= 1;
-    for (L = LH; L < 64 && L < (uint64_t)heads * LH; L <<= 1) {}
-    const uint32_t per = L / LH;                       // heads per block
-    const uint32_t chunks = (heads + per - 1) / per;   // blockIdx.y; a launch takes at most 65535 of them
 #define PYGIM_SA_LAUNCH(NP)                                                                                                                                    \
-    for (uint32_t c0 = 0; c0 < chunks; c0 += 65535u)                                                                                                           \
-    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP>), dim3(blocks, chunks - c0 < 65535u ? chunks - c0 : 65535u), dim3(256), 0, st, rowptr, colind, nrows, nnz, \
-                       Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * per, scale, LH, L, out, ldo, lse, ws, ws_stat)
+    for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                                  \
+    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, rowptr,  \
+                       colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * g.per, scale, g.LH, g.L, out, ldo, lse, ws, ws_stat)
     constexpr uint32_t MAX_NP = (SA_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);   // only the piece counts a head of SA_MAX_HEAD can need
-    if (np == 1) PYGIM_SA_LAUNCH(1);
+    if (g.npl == 1) PYGIM_SA_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
-        if (np == 2) PYGIM_SA_LAUNCH(2);
+        if (g.npl == 2) PYGIM_SA_LAUNCH(2);
     if constexpr (MAX_NP >= 4)
-        if (np == 4) PYGIM_SA_LAUNCH(4);
+        if (g.npl == 4) PYGIM_SA_LAUNCH(4);
 #undef PYGIM_SA_LAUNCH
 }
 
@@ -239,10 +249,11 @@ inline void launch_sparse_attention(const uint32_t *rowptr, const uint32_t *coli
     if (nnz == 0) return;
     T *ws = (T *)workspace;
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
-    const bool vec = (h / heads) % V == 0 && ldq % V == 0 && ldk % V == 0 && ldv % V == 0 && ldo % V == 0 && (uintptr_t)Q % 16 == 0 &&
-                     (uintptr_t)K % 16 == 0 && (uintptr_t)Vm % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
-    if (vec) launch_sa_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, st);
-    else launch_sa_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, st);
+    const bool aligned = ldq % V == 0 && ldk % V == 0 && ldv % V == 0 && ldo % V == 0 && (uintptr_t)Q % 16 == 0 && (uintptr_t)K % 16 == 0 &&
+                         (uintptr_t)Vm % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
+    const LaunchShape g = head_gather_shape(h, heads, V, aligned);
+    if (g.vec > 1) launch_sa_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, st);
+    else launch_sa_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

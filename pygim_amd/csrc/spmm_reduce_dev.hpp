@@ -144,27 +144,27 @@ __global__ __launch_bounds__(256) void k_spmm_reduce_bwd(const uint32_t *__restr
 
 template <typename T, int VEC>
 inline void launch_spmm_reduce_bwd_v(const uint32_t *rowptr_t, const uint32_t *rows_t, const int32_t *perm, uint32_t ncols, const T *values, const T *G,
-                                     uint64_t ldg, const int32_t *arg, uint32_t h, T *dX, uint64_t ldd, hipStream_t st) {
-    const uint32_t pieces = (h + VEC - 1) / VEC;
-    if (pieces <= 64) {
-        uint32_t L = 1;
-        while (L < pieces) L <<= 1;
-        hipLaunchKernelGGL((k_spmm_reduce_bwd<T, VEC, 1>), dim3((unsigned)(((uint64_t)ncols * L + 255) / 256)), dim3(256), 0, st, rowptr_t, rows_t, perm,
-                           ncols, values, G, ldg, arg, h, L, dX, ldd);
+                                     uint64_t ldg, const int32_t *arg, uint32_t h, T *dX, uint64_t ldd, const LaunchShape &g, hipStream_t st) {
+    if (g.npl == 1) {
+        hipLaunchKernelGGL((k_spmm_reduce_bwd<T, VEC, 1>), dim3((unsigned)(((uint64_t)ncols * g.L + 255) / 256)), dim3(256), 0, st, rowptr_t, rows_t, perm,
+                           ncols, values, G, ldg, arg, h, g.L, dX, ldd);
     } else {
-        hipLaunchKernelGGL((k_spmm_reduce_bwd<T, VEC, 2>), dim3((unsigned)(((uint64_t)ncols * 64 + 255) / 256), (pieces + 127) / 128), dim3(256), 0, st,
+        hipLaunchKernelGGL((k_spmm_reduce_bwd<T, VEC, 2>), dim3((unsigned)(((uint64_t)ncols * 64 + 255) / 256), g.chunks), dim3(256), 0, st,
                            rowptr_t, rows_t, perm, ncols, values, G, ldg, arg, h, 64u, dX, ldd);
     }
 }
+
+// the row walkers' layout, except that L lanes (not the whole wave) own an output row up to 64 pieces
+inline LaunchShape spmm_reduce_bwd_shape(uint32_t h, uint32_t V, bool aligned) { return row_gather_shape(h, h, V, aligned, 64); }
 
 template <typename T>
 inline void launch_spmm_reduce_bwd(const uint32_t *rowptr_t, const uint32_t *rows_t, const int32_t *perm, uint32_t ncols, const T *values, const T *G,
                                    uint64_t ldg, const int32_t *arg, uint32_t h, T *dX, uint64_t ldd, hipStream_t st) {
     constexpr uint32_t V = 16 / sizeof(T);
     if (ncols == 0) return;
-    const bool vec = h % V == 0 && ldg % V == 0 && ldd % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)dX % 16 == 0;
-    if (vec) launch_spmm_reduce_bwd_v<T, (int)V>(rowptr_t, rows_t, perm, ncols, values, G, ldg, arg, h, dX, ldd, st);
-    else launch_spmm_reduce_bwd_v<T, 1>(rowptr_t, rows_t, perm, ncols, values, G, ldg, arg, h, dX, ldd, st);
+    const LaunchShape g = spmm_reduce_bwd_shape(h, V, ldg % V == 0 && ldd % V == 0 && (uintptr_t)G % 16 == 0 && (uintptr_t)dX % 16 == 0);
+    if (g.vec > 1) launch_spmm_reduce_bwd_v<T, (int)V>(rowptr_t, rows_t, perm, ncols, values, G, ldg, arg, h, dX, ldd, g, st);
+    else launch_spmm_reduce_bwd_v<T, 1>(rowptr_t, rows_t, perm, ncols, values, G, ldg, arg, h, dX, ldd, g, st);
 }
 
 }  // namespace pygim

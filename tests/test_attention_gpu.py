@@ -86,15 +86,15 @@ def test_spmm_values_parity_over_three_feature_chunks(rng):
     check_spmm_values_parity(rng, torch.float32, 300, "small")
 
 
-def check_spmm_values_parity(rng, dtype, h, graph):
+def check_spmm_values_parity(rng, dtype, h, graph, head_counts=(1, 4, 8), ldxs=None):
     n, m, rowptr, col = GRAPHS[graph](rng)
     rp, cc = dev_csr(rowptr, col)
     nnz = len(col)
     vec = 16 // torch.empty(0, dtype=dtype).element_size()
-    for heads in [k for k in (1, 4, 8) if h % k == 0]:
+    for heads in [k for k in head_counts if h % k == 0]:
         val = torch.from_numpy(rng.uniform(-2, 2, size=(nnz, heads))).to(DEV, dtype)
         # a contiguous X, a wider row stride that keeps 16-byte alignment, and one that breaks it
-        for ldx in ((h, h + 2 * vec, h + 1) if graph == "small" else (h,)):
+        for ldx in ldxs or ((h, h + 2 * vec, h + 1) if graph == "small" else (h,)):
             X = torch.from_numpy(rng.uniform(-1, 1, size=(m, ldx))).to(DEV, dtype)
             out = call_spmm_values(dtype, n, rp, cc, val, heads, X, h)
             assert not torch.isnan(out).any(), "a row was not written"
@@ -138,10 +138,12 @@ def test_spmm_values_strided_out_nnz0_and_bad_arguments(rng):
         _lib.edge_softmax(_lib.FLT32, n, rp.data_ptr(), len(col), val.data_ptr(), heads, o.data_ptr(), ws.data_ptr(), 16)
 
 
-def call_softmax(dtype, n, rp, nnz, a, heads, b=None):
+def call_softmax(dtype, n, rp, nnz, a, heads, b=None, out=None):
+    """a, b, out: [nnz, heads] contiguous (out: NaN-filled before the call)"""
     code = pim_ops.DTYPE_CODE[dtype]
     ws = torch.empty(max(_lib.edge_softmax_workspace(code, n, nnz, heads), 16), dtype=torch.uint8, device=DEV)
-    out = torch.full((nnz, heads), float("nan"), dtype=dtype, device=DEV)
+    if out is None:
+        out = torch.full((nnz, heads), float("nan"), dtype=dtype, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
     if b is None:
         _lib.edge_softmax(code, n, rp.data_ptr(), nnz, a.data_ptr(), heads, out.data_ptr(), ws.data_ptr(), ws.numel(), st)

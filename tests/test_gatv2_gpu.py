@@ -380,18 +380,29 @@ def test_gradients_in_bfloat16(rng):
       dx_dst = sum_e ds att lrelu'(z):    u |ref| + sum_e Wd |att| lrelu' + EPS sum_e |t|        (the last: the float32 sum)
       dx_src = sum_e (p G + ds att lrelu'):  u |ref| + (rel + EPS) sum_e p |G| + sum_e Wd |att| lrelu' + EPS sum_e |t|
       datt   = sum_e ds lrelu(z):         sum_e Wd |lrelu(z)| + EPS sum_e |ds lrelu(z)|          (float32: no rounding to 16 bits)"""
-    dtype, u, eps = torch.bfloat16, 2.0 ** -8, 1e-5
     n, m, rowptr, col = small_graph(rng)
+    check_gradients_16_bit(torch.bfloat16, n, m, rowptr, col, 64, 4)
+
+
+def wrapper_gradients(g, Xd, Xs, att, G, h, heads):
+    """(dx_dst, dx_src, datt) through the autograd wrapper"""
+    dev = [t.to(DEV).requires_grad_() for t in (Xd, Xs, att)]
+    out = gatv2_aggregate(g, *dev, heads=heads, negative_slope=SLOPE)
+    out.backward(G.to(DEV))
+    assert out.dtype == Xd.dtype and [t.grad.dtype for t in dev] == [Xd.dtype, Xd.dtype, torch.float32]
+    return [t.grad for t in dev]
+
+
+def check_gradients_16_bit(dtype, n, m, rowptr, col, h, heads, run=wrapper_gradients):
+    """the bound of test_gradients_in_bfloat16 (u = 2^-8 / 2^-11) for any graph and head shape; run(g, Xd, Xs, att, G, h, heads) with host
+    operands -> the three gradients on the device"""
+    u, eps = U[dtype], 1e-5
     g = EdgeGraph(torch.from_numpy(rowptr), torch.from_numpy(col), (n, m))
-    h, heads = 64, 4
     hd = h // heads
     torch.manual_seed(22)
     Xd, Xs, G = (torch.randn(r, h).to(dtype) for r in (n, m, n))
     att = torch.randn(h) * hd ** -0.5
-    dev = [t.to(DEV).requires_grad_() for t in (Xd, Xs, att)]
-    out = gatv2_aggregate(g, *dev, heads=heads, negative_slope=SLOPE)
-    out.backward(G.to(DEV))
-    assert out.dtype == dtype and [t.grad.dtype for t in dev] == [dtype, dtype, torch.float32]
+    grads = run(g, Xd, Xs, att, G, h, heads)
     cpu = [t.double().requires_grad_() for t in (Xd, Xs, att)]
     ref_out = ref_gatv2(rowptr, col, *cpu, heads, n, SLOPE)
     ref_out.backward(G.double())
@@ -422,10 +433,11 @@ def test_gradients_in_bfloat16(rng):
     bound_dst = torch.zeros(n, h, dtype=torch.float64).index_add_(0, row, t_mag + eps * t_abs)
     bound_src = torch.zeros(m, h, dtype=torch.float64).index_add_(0, cc, t_mag + eps * t_abs + (rel + eps) * wide(P) * gg[row].abs())
     bound_att = (wide(Wd) * lz.abs() + eps * wide(ds.abs()) * lz.abs()).sum(0)
-    for name, d, c, bound, uu in (("x_dst", dev[0], cpu[0], bound_dst, u), ("x_src", dev[1], cpu[1], bound_src, u), ("att", dev[2], cpu[2], bound_att, 0.0)):
-        err = (d.grad.cpu().double() - c.grad).abs()
+    for name, d, c, bound, uu in (("x_dst", grads[0], cpu[0], bound_dst, u), ("x_src", grads[1], cpu[1], bound_src, u), ("att", grads[2], cpu[2], bound_att, 0.0)):
+        assert not torch.isnan(d).any(), f"d{name}: not written"
+        err = (d.cpu().double() - c.grad).abs()
         full = uu * c.grad.abs() + bound + 2.0 ** -24
-        print(f"gatv2_aggregate bfloat16 d{name}: max err / bound = {(err / full).max().item():.3f}")
+        print(f"gatv2_aggregate {dtype} h={h} heads={heads} d{name}: max err / bound = {(err / full).max().item():.3f}")
         assert torch.all(err <= full), name
 
 

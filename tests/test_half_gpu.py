@@ -117,19 +117,21 @@ def features(rng, ld, dtype, kind):
     return x.abs() if kind == "abs" else x
 
 
-def call_values(dtype, rp, cc, val, heads, X, h, op=None):
-    """pygim_spmm_values (op None) or pygim_spmm_reduce MEAN on 16-bit X [M, ldx]; val float32 (None: unit weights, mean only)"""
+def call_values(dtype, rp, cc, val, heads, X, h, op=None, out=None):
+    """pygim_spmm_values (op None) or pygim_spmm_reduce MEAN on 16-bit X [M, ldx]; val float32 (None: unit weights, mean only); out:
+    [N, ldo], NaN-filled before the call"""
     nnz = cc.numel()
-    out = torch.full((N, h), float("nan"), dtype=dtype, device=DEV)
+    if out is None:
+        out = torch.full((N, h), float("nan"), dtype=dtype, device=DEV)
     stream = torch.cuda.current_stream().cuda_stream
     if op is None:
         ws = torch.empty(max(_lib.spmm_values_workspace(CODE[dtype], N, nnz, h, heads), 16), dtype=torch.uint8, device=DEV)
-        _lib.spmm_values(CODE[dtype], N, rp.data_ptr(), cc.data_ptr(), nnz, val.data_ptr(), heads, X.data_ptr(), X.stride(0), h, out.data_ptr(), h,
+        _lib.spmm_values(CODE[dtype], N, rp.data_ptr(), cc.data_ptr(), nnz, val.data_ptr(), heads, X.data_ptr(), X.stride(0), h, out.data_ptr(), out.stride(0),
                          ws.data_ptr(), ws.numel(), stream)
     else:
         ws = torch.empty(max(_lib.spmm_reduce_workspace(CODE[dtype], op, N, nnz, h), 16), dtype=torch.uint8, device=DEV)
         _lib.spmm_reduce(CODE[dtype], op, N, rp.data_ptr(), cc.data_ptr(), nnz, 0 if val is None else val.data_ptr(), X.data_ptr(), X.stride(0), h,
-                         out.data_ptr(), h, 0, ws.data_ptr(), ws.numel(), stream)
+                         out.data_ptr(), out.stride(0), 0, ws.data_ptr(), ws.numel(), stream)
     torch.cuda.synchronize()
     return out
 
@@ -175,6 +177,14 @@ def within(got, want, mag, u, tol32, tag):
 @pytest.mark.parametrize("h,heads", WIDTHS)
 def test_random_sums_and_means_meet_the_bound(rng, dtype, h, heads):
     """X ~ N(0, 1) rounded to the type (and |X|: same-sign products in the long rows), values in (0.5, 1); the mean with and without values"""
+    rp, cc, val = check_random_sums_and_means(rng, dtype, h, heads)
+    if heads == 1:   # the wrapper: the bits of the C ABI
+        X = features(rng, h, dtype, "normal")
+        g = EdgeGraph(rp, cc, (N, M))
+        assert torch.equal(spmm_reduce(g, X, "mean", value=val[:, 0]), call_values(dtype, rp, cc, val, 1, X, h, op=_lib.REDUCE_MEAN))
+
+
+def check_random_sums_and_means(rng, dtype, h, heads):
     rowptr, col, rp, cc = graph("main")
     cnt = torch.from_numpy(np.maximum(np.diff(rowptr), 1)).to(DEV).double().unsqueeze(1)
     val = torch.from_numpy(rng.uniform(0.5, 1.0, size=(len(col), heads)).astype(np.float32)).to(DEV)
@@ -190,19 +200,17 @@ def test_random_sums_and_means_meet_the_bound(rng, dtype, h, heads):
                     mean = call_values(dtype, rp, cc, v, 1, X, h, op=_lib.REDUCE_MEAN)
                     r1, m1 = (ref, mag) if v is not None else spmm_reference(N, rowptr, col, torch.ones_like(val), 1, X, h)
                     assert within(mean, r1 / cnt, m1 / cnt, U[dtype], 1e-5, f"mean {dtype} {kind} h={h} ldx={ld} values={v is not None}")
-    if heads == 1:   # the wrapper: the bits of the C ABI
-        X = features(rng, h, dtype, "normal")
-        g = EdgeGraph(rp, cc, (N, M))
-        assert torch.equal(spmm_reduce(g, X, "mean", value=val[:, 0]), call_values(dtype, rp, cc, val, 1, X, h, op=_lib.REDUCE_MEAN))
+    return rp, cc, val
 
 
-def call_gat(dtype, rp, cc, a_dst, a_src, heads, slope, X, h, want_lse=True):
+def call_gat(dtype, rp, cc, a_dst, a_src, heads, slope, X, h, want_lse=True, out=None):
     nnz = cc.numel()
     ws = torch.empty(max(_lib.gat_aggregate_workspace(CODE[dtype], N, nnz, h, heads), 16), dtype=torch.uint8, device=DEV)
-    out = torch.full((N, h), float("nan"), dtype=dtype, device=DEV)
+    if out is None:
+        out = torch.full((N, h), float("nan"), dtype=dtype, device=DEV)
     lse = torch.full((N, heads), float("nan"), dtype=torch.float32, device=DEV) if want_lse else None
     _lib.gat_aggregate(CODE[dtype], N, rp.data_ptr(), cc.data_ptr(), nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope, X.data_ptr(), X.stride(0), h,
-                       out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+                       out.data_ptr(), out.stride(0), lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return out, lse
 

@@ -266,6 +266,11 @@ def test_strided_out_nnz0_and_bad_arguments(rng):
 @pytest.mark.parametrize("h", [9, 256])
 @pytest.mark.parametrize("graph", ["small", "hub"])
 def test_backward_parity(rng, dtype, h, graph):
+    check_backward_parity(rng, dtype, h, graph)
+
+
+def check_backward_parity(rng, dtype, h, graph, view=lambda name, t: t):
+    """view(name, tensor): the buffer G / dX is handed over in (another row stride or start; NaN around it)"""
     n, m, rowptr, col = GRAPHS[graph](rng)
     g = EdgeGraph(torch.from_numpy(rowptr), torch.from_numpy(col), (n, m))
     gt, perm = g.transposed()
@@ -279,9 +284,10 @@ def test_backward_parity(rng, dtype, h, graph):
         _, arg = call_reduce(dtype, OP["max"], n, g.rowptr, g.col, val, X, h, True)
 
         def run():
-            dX = torch.full((m, h), float("nan"), dtype=dtype, device=DEV)
+            dX = view("dX", torch.full((m, h), float("nan"), dtype=dtype, device=DEV))
+            Gv = view("G", G)
             _lib.spmm_reduce_backward(code, m, gt.rowptr.data_ptr(), gt.col.data_ptr(), perm32.data_ptr(), nnz, 0 if val is None else val.data_ptr(),
-                                      G.data_ptr(), h, arg.data_ptr(), h, dX.data_ptr(), h, torch.cuda.current_stream().cuda_stream)
+                                      Gv.data_ptr(), Gv.stride(0), arg.data_ptr(), h, dX.data_ptr(), dX.stride(0), torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             return dX
 
