@@ -61,7 +61,7 @@ typedef enum {
     PYGIM_FLT32 = 4,
     PYGIM_DBL64 = 5,
     /* 16-bit FEATURE types (IEEE binary16, bfloat16).  Valid only for pygim_sddmm, pygim_spmm_values, pygim_gat_aggregate,
-     * pygim_sparse_attention, pygim_gatv2_aggregate, pygim_gatv2_backward, pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
+     * pygim_sparse_attention, pygim_gatv2_aggregate, pygim_gatv2_backward (and the *_dropout forms of these four), pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
      * point -- group creation, edge softmax, the max / min reductions and their backward, the quantisers -- rejects them like
      * an unknown type. */
     PYGIM_FLT16 = 6,
@@ -363,6 +363,66 @@ int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t
                          int64_t h, int64_t heads, double negative_slope, const void *G, int64_t ldg, const void *lse,
                          const void *delta, void *d_own, int64_t ldd, void *datt /* [h]; NULL when transposed */,
                          void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- attention dropout: dropout on the attention coefficients, inside the fused kernels ----
+ * The `dropout=` of PyG's GATConv, GATv2Conv and TransformerConv.  With pr[e, k] the softmax probability of stored entry e and head k
+ * and p the rate, the coefficients are dropped after the softmax and before the product with the gathered row:
+ *     w[e, k]   = keep(e, k) ? 1 / (1 - p) : 0
+ *     out[r, f] = sum_e pr[e, k] * w[e, k] * v[e, f]                      k = head of f
+ * The running maximum, the normalisation l and lse run over ALL entries, dropped ones included: lse has the bits of the call without
+ * dropout.  A non-empty row whose entries are all dropped for a head stores exact zeros for that head (never NaN); scores of -inf
+ * stay masked as in the base calls.  Backward, with G = dout:
+ *     dpr[e, k] = w[e, k] * sum_{f in head k} G[r, f] * v[e, f]           delta[r, k] = sum_e pr * dpr = sum_{f in head k} G[r, f] * out[r, f]
+ *     ds        = pr * (dpr - delta[r, k])                                dv[c, f]    = sum_{e with col c} pr * w * G[r, f]
+ * delta is still formed from G and out, because out already contains w.
+ *
+ * The mask is a pure function of (seed, entry index in A, head).  It keeps no state and depends neither on the launch shape nor on
+ * the direction the CSR is walked.  All arithmetic is uint32, mod 2^32; seed = seed_hi:seed_lo is 64 bits; e is the index of the
+ * entry in the stored order of A (0 .. nnz - 1), k the head:
+ *     fmix(x):    x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *     u(e, k)    = fmix( fmix(e ^ seed_lo) + seed_hi + k * 0x9E3779B9 )
+ *     keep(e, k) = u(e, k) >= T,      T = min(2^32 - 1, floor(p * 2^32)),      0 <= p < 1
+ * (two 32-bit multiplies per fmix; the inner fmix depends on the entry alone).  One inline function, attn_dropout_keep of
+ * pygim_amd/csrc/attn_dropout_dev.hpp, is what every kernel and pygim_attention_dropout_host call.
+ *
+ *   pygim_gat_aggregate_dropout, pygim_sparse_attention_dropout, pygim_gatv2_aggregate_dropout: the base entry point with (p, seed)
+ *     appended.  Everything of the base contract holds: types, pointers, strides, bounds (with p[e] read as pr * w), determinism, the
+ *     launch shape (pygim_gather_launch_shape of the base kind answers for them).  The EXISTING workspace functions serve them:
+ *     pygim_gat_aggregate_workspace, pygim_sparse_attention_workspace, pygim_gatv2_aggregate_workspace.
+ *   pygim_gatv2_backward_dropout: pygim_gatv2_backward with (entry_ids, p, seed) appended; pygim_gatv2_backward_workspace serves it.
+ *     dp becomes w * sum G x_src, the transposed direction accumulates pr * w * G + t.  entry_ids (int32 [nnz], device): the index in A of
+ *     every entry of the CSR that is walked -- for transposed = 1 the permutation that made A^T (entry i of A^T is entry entry_ids[i]
+ *     of A: the stable sort of A's entries by column); NULL means identity, for the CSR of A itself.  delta comes from the caller as
+ *     before, from G and the out of the dropout forward.
+ *   p = 0 launches the instantiation of the base entry point and stores its bits (seed and entry_ids are not read).  p < 0, p >= 1
+ *     or NaN: PYGIM_ERR_INVALID, checked before anything else (no device is needed for that answer).
+ *   pygim_attention_dropout_mask: mask[i, k] = w[entry_ids ? entry_ids[i] : i, k] for i < nnz, k < heads, [nnz, heads] contiguous,
+ *     FLT32 or DBL64, device pointers, enqueued on `stream`.  What the unfused compositions and composed backwards multiply by.
+ *   pygim_attention_dropout_host: keep[i * heads + k] = keep(e0 + i, k) as 0 / 1 bytes, host memory, for i < nnz.  Host only: it needs
+ *     no device and no pygim_init_*; it calls the same inline function as the kernels (e0 + nnz <= 2^32).
+ * Not covered: a captured graph replays the seed it was captured with; multi-GPU; heads wider than 256 features (the fused
+ * sparse-attention / GATv2 kernels reject them with or without dropout: the unfused composition with the mask kernel serves them). */
+int pygim_gat_aggregate_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                                const void *a_dst, const void *a_src, int64_t heads, double negative_slope, const void *X,
+                                int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
+                                int64_t workspace_bytes, void *stream, double p, uint64_t seed);
+int pygim_sparse_attention_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                                   const void *Q, int64_t ldq, const void *K, int64_t ldk, const void *V, int64_t ldv,
+                                   int64_t h, int64_t heads, double scale, void *out, int64_t ldo, void *lse,
+                                   void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed);
+int pygim_gatv2_aggregate_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                                  const void *x_dst, int64_t ld_dst, const void *x_src, int64_t ld_src, const void *att,
+                                  int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo, void *lse,
+                                  void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed);
+int pygim_gatv2_backward_dropout(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind,
+                                 int64_t nnz, const void *x_own, int64_t ld_own, const void *x_oth, int64_t ld_oth,
+                                 const void *att, int64_t h, int64_t heads, double negative_slope, const void *G, int64_t ldg,
+                                 const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace,
+                                 int64_t workspace_bytes, void *stream, const int32_t *entry_ids /* [nnz] or NULL */, double p,
+                                 uint64_t seed);
+int pygim_attention_dropout_mask(int dtype, int64_t nnz, int64_t heads, const int32_t *entry_ids /* [nnz] or NULL */, double p,
+                                 uint64_t seed, void *mask /* [nnz, heads] */, void *stream);
+int pygim_attention_dropout_host(int64_t nnz, int64_t heads, int64_t e0, double p, uint64_t seed, uint8_t *keep /* [nnz, heads] */);
 
 /* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
  *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1

@@ -14,6 +14,6 @@ Layout:
 """
 __version__ = "0.1.0"
 
-from .attention import EdgeGraph, edge_softmax, gat_aggregate, gatv2_aggregate, sparse_attention, spmm_values  # noqa: E402,F401
+from .attention import EdgeGraph, dropout_mask, edge_softmax, gat_aggregate, gatv2_aggregate, sparse_attention, spmm_values  # noqa: E402,F401
 from .autograd import sddmm  # noqa: E402,F401
 from .reduce import spmm_reduce  # noqa: E402,F401

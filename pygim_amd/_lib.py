@@ -25,6 +25,8 @@ EXPORTS = [
     "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
     "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward", "pygim_gather_launch_shape",
+    "pygim_gat_aggregate_dropout", "pygim_sparse_attention_dropout", "pygim_gatv2_aggregate_dropout", "pygim_gatv2_backward_dropout",
+    "pygim_attention_dropout_mask", "pygim_attention_dropout_host",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -94,6 +96,14 @@ def lib():
                                            c_i64, vp, vp, c_i64, vp]
         L.pygim_gatv2_backward_workspace.argtypes = [c_int, c_i64, c_i64, c_i64, c_i64]
         L.pygim_gatv2_backward_workspace.restype = c_i64
+        # attention dropout: the base signature, then (entry_ids,) p, seed
+        c_dbl, c_u64 = ctypes.c_double, ctypes.c_uint64
+        L.pygim_gat_aggregate_dropout.argtypes = list(L.pygim_gat_aggregate.argtypes) + [c_dbl, c_u64]
+        L.pygim_sparse_attention_dropout.argtypes = list(L.pygim_sparse_attention.argtypes) + [c_dbl, c_u64]
+        L.pygim_gatv2_aggregate_dropout.argtypes = list(L.pygim_gatv2_aggregate.argtypes) + [c_dbl, c_u64]
+        L.pygim_gatv2_backward_dropout.argtypes = list(L.pygim_gatv2_backward.argtypes) + [vp, c_dbl, c_u64]
+        L.pygim_attention_dropout_mask.argtypes = [c_int, c_i64, c_i64, vp, c_dbl, c_u64, vp, vp]
+        L.pygim_attention_dropout_host.argtypes = [c_i64, c_i64, c_i64, c_dbl, c_u64, vp]
         L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
@@ -321,6 +331,60 @@ def gatv2_backward(dtype, transposed, nrows, rowptr_ptr, col_ptr, nnz, own_ptr, 
     check(lib().pygim_gatv2_backward(int(dtype), int(transposed), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(own_ptr), int(ld_own),
                                      _vp(oth_ptr), int(ld_oth), _vp(att_ptr), int(h), int(heads), float(negative_slope), _vp(g_ptr), int(ldg),
                                      _vp(lse_ptr), _vp(delta_ptr), _vp(d_own_ptr), int(ldd), _vp(datt_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+# ---- attention dropout (include/pygim_hip.h): the base calls with a rate p in [0, 1) and a 64-bit seed; p = 0 is the base call.  The
+# base entry points' *_workspace functions serve them.
+def _seed(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def gat_aggregate_dropout(dtype, nrows, rowptr_ptr, col_ptr, nnz, a_dst_ptr, a_src_ptr, heads, negative_slope, x_ptr, ldx, h, out_ptr, ldo, lse_ptr,
+                          ws_ptr, ws_bytes, stream, p, seed):
+    """gat_aggregate with the probabilities dropped at rate p by the mask of (seed, entry, head) after the softmax"""
+    check(lib().pygim_gat_aggregate_dropout(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(a_dst_ptr), _vp(a_src_ptr),
+                                            int(heads), float(negative_slope), _vp(x_ptr), int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr),
+                                            _vp(ws_ptr), int(ws_bytes), _vp(stream), float(p), _seed(seed)))
+
+
+def sparse_attention_dropout(dtype, nrows, rowptr_ptr, col_ptr, nnz, q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, h, heads, scale, out_ptr, ldo, lse_ptr,
+                             ws_ptr, ws_bytes, stream, p, seed):
+    """sparse_attention with the probabilities dropped at rate p by the mask of (seed, entry, head) after the softmax"""
+    check(lib().pygim_sparse_attention_dropout(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(q_ptr), int(ldq), _vp(k_ptr),
+                                               int(ldk), _vp(v_ptr), int(ldv), int(h), int(heads), float(scale), _vp(out_ptr), int(ldo),
+                                               _vp(lse_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream), float(p), _seed(seed)))
+
+
+def gatv2_aggregate_dropout(dtype, nrows, rowptr_ptr, col_ptr, nnz, xd_ptr, ld_dst, xs_ptr, ld_src, att_ptr, h, heads, negative_slope, out_ptr, ldo,
+                            lse_ptr, ws_ptr, ws_bytes, stream, p, seed):
+    """gatv2_aggregate with the probabilities dropped at rate p by the mask of (seed, entry, head) after the softmax"""
+    check(lib().pygim_gatv2_aggregate_dropout(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(xd_ptr), int(ld_dst),
+                                              _vp(xs_ptr), int(ld_src), _vp(att_ptr), int(h), int(heads), float(negative_slope), _vp(out_ptr),
+                                              int(ldo), _vp(lse_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream), float(p), _seed(seed)))
+
+
+def gatv2_backward_dropout(dtype, transposed, nrows, rowptr_ptr, col_ptr, nnz, own_ptr, ld_own, oth_ptr, ld_oth, att_ptr, h, heads, negative_slope,
+                           g_ptr, ldg, lse_ptr, delta_ptr, d_own_ptr, ldd, datt_ptr, ws_ptr, ws_bytes, stream, entry_ids_ptr, p, seed):
+    """gatv2_backward of a forward that ran with dropout (p, seed); entry_ids_ptr: int32 [nnz], the index in A of every entry of the CSR
+    that is walked (the perm of the transposed CSR), 0 for the CSR of A itself"""
+    check(lib().pygim_gatv2_backward_dropout(int(dtype), int(transposed), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(own_ptr),
+                                             int(ld_own), _vp(oth_ptr), int(ld_oth), _vp(att_ptr), int(h), int(heads), float(negative_slope),
+                                             _vp(g_ptr), int(ldg), _vp(lse_ptr), _vp(delta_ptr), _vp(d_own_ptr), int(ldd), _vp(datt_ptr),
+                                             _vp(ws_ptr), int(ws_bytes), _vp(stream), _vp(entry_ids_ptr), float(p), _seed(seed)))
+
+
+def attention_dropout_mask(dtype, nnz, heads, entry_ids_ptr, p, seed, mask_ptr, stream=0):
+    """mask [nnz, heads] (FLT32 / DBL64, device) = 1 / (1 - p) where entry (entry_ids[i], or i when entry_ids_ptr is 0) and head are kept, else 0"""
+    check(lib().pygim_attention_dropout_mask(int(dtype), int(nnz), int(heads), _vp(entry_ids_ptr), float(p), _seed(seed), _vp(mask_ptr), _vp(stream)))
+
+
+def attention_dropout_host(nnz, heads, e0, p, seed):
+    """the keep mask of entries e0 .. e0 + nnz - 1 as a numpy uint8 [nnz, heads], computed on the host by the kernels' own function (no device)"""
+    import numpy as np
+
+    keep = np.empty((int(nnz), int(heads)), dtype=np.uint8)
+    check(lib().pygim_attention_dropout_host(int(nnz), int(heads), int(e0), float(p), _seed(seed), keep.ctypes.data if keep.size else None))
+    return keep
 
 
 def spmm_reduce_workspace(dtype, op, nrows, nnz, h):

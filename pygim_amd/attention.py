@@ -29,6 +29,16 @@ in 16 bits: edge values, ``a_dst`` / ``a_src``, ``lse``, every partial sum and t
 16-bit values and node terms), and a result row is rounded once, to nearest even, where it is stored.  ``edge_softmax`` stays float32 /
 float64.
 
+Attention dropout (``dropout=`` of PyG's GATConv, GATv2Conv and TransformerConv): ``gat_aggregate``, ``sparse_attention`` and
+``gatv2_aggregate`` take ``dropout=0.0, seed=None``.  The coefficients are dropped after the softmax and before the product with the
+gathered row, inside the gather: ``out[r] = sum_e pr[e] * w[e] * v[e]`` with ``w = 1 / (1 - dropout)`` for a kept (entry, head) and 0 for a
+dropped one, while the maximum, the normalisation and ``lse`` run over all entries.  The mask is a stateless hash of ``(seed, entry index
+in A, head)`` (include/pygim_hip.h states it bit for bit; :func:`dropout_mask` returns it), so the fused forward, the composed and fused
+backwards and the ``fused=False`` compositions drop the same entries for one seed; ``seed=None`` draws one per call from torch's default
+CPU generator (``torch.manual_seed`` reproduces a run) and the backward reuses it.  ``dropout=0`` launches exactly what the call without
+the argument launches.  Not covered by attention dropout: a captured graph replays the seed it was captured with; multi-GPU; heads wider
+than 256 features get it through the unfused composition only.
+
 Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph, 16-bit device groups
 (``mul``), 16-bit ``edge_softmax`` and 16-bit max / min; for ``sparse_attention`` also a fused backward kernel, edge features / ``beta``
 of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass composition); for
@@ -137,6 +147,13 @@ class EdgeGraph:
             self._t = (EdgeGraph._bare(rowptr_t.to(torch.int32), col_t, row_t, self.ncols, self.nrows), perm)
         return self._t
 
+    def entry_ids_t(self) -> torch.Tensor:
+        """``perm`` of :meth:`transposed` as int32, cached: the index in A of every entry of A^T, what pygim_gatv2_backward_dropout and
+        pygim_attention_dropout_mask take as ``entry_ids``"""
+        if getattr(self, "_perm32", None) is None:
+            self._perm32 = self.transposed()[1].to(torch.int32).contiguous()
+        return self._perm32
+
 
 def _workspace(nbytes: int, dev) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
@@ -144,6 +161,41 @@ def _workspace(nbytes: int, dev) -> torch.Tensor:
 
 def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+
+
+def _dropout_rate(name: str, p) -> float:
+    p = float(p)
+    if not 0.0 <= p < 1.0:   # NaN included
+        raise ValueError(f"{name}: dropout must lie in [0, 1), got {p}")
+    return p
+
+
+def _dropout_seed(seed) -> int:
+    """the 64-bit seed of a call: the caller's, or two 32-bit draws from torch's default CPU generator (``torch.manual_seed`` reproduces it)"""
+    if seed is not None:
+        return int(seed) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
+    return (hi << 32) | lo
+
+
+def dropout_mask(graph, heads: int, p: float, seed: int, dtype=torch.float32, transposed: bool = False) -> torch.Tensor:
+    """the weights of attention dropout, ``[nnz, heads]`` on the graph's device: ``1 / (1 - p)`` where (entry, head) is kept, 0 where it
+    is dropped (pygim_attention_dropout_mask; the mask function is specified in include/pygim_hip.h).  A pure function of
+    ``(seed, entry index in A, head)``: the fused kernels with the same ``p`` and ``seed`` drop the same entries.  ``transposed=True``
+    gives the rows in the order of ``EdgeGraph.transposed()`` (row i belongs to entry ``perm[i]`` of A).  float32 or float64."""
+    p = _dropout_rate("dropout_mask", p)
+    g = EdgeGraph.of(graph)
+    heads = int(heads)
+    if heads < 1:
+        raise ValueError(f"dropout_mask: heads must be at least 1, got {heads}")
+    if dtype not in FLOAT_TYPES:
+        raise TypeError(f"dropout_mask: dtype must be float32 or float64, got {dtype}")
+    L, code = _backend()
+    w = torch.empty((g.nnz, heads), dtype=dtype, device=g.device)
+    if g.nnz > 0:
+        ids = g.entry_ids_t().data_ptr() if transposed else 0
+        L.attention_dropout_mask(code[dtype], g.nnz, heads, ids, p, _dropout_seed(seed), w.data_ptr(), _stream(g.device))
+    return w
 
 
 def _run_spmm_values(g: EdgeGraph, value: torch.Tensor, X: torch.Tensor, heads: int) -> torch.Tensor:
@@ -262,7 +314,7 @@ def edge_softmax(graph, scores: torch.Tensor) -> torch.Tensor:
     return P.reshape(scores.shape).to(home)
 
 
-def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool):
+def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool, p: float = 0.0, seed: int = 0):
     """a_dst [nrows, heads], a_src [ncols, heads] (float32 beside 16-bit X, else X's dtype), X [ncols, h] contiguous on g.device ->
     (out [nrows, h] in X's dtype, lse [nrows, heads] in a_dst's or None)"""
     L, _ = _backend()
@@ -273,19 +325,23 @@ def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, 
     if g.nrows == 0:
         return out, lse
     ws = _workspace(L.gat_aggregate_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
-    L.gat_aggregate(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
-                    X.data_ptr(), X.stride(0), h, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    args = (dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
+            X.data_ptr(), X.stride(0), h, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    if p > 0.0:
+        L.gat_aggregate_dropout(*args, p, seed)
+    else:   # exactly the call without the argument
+        L.gat_aggregate(*args)
     return out, lse
 
 
 class GatAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, a_dst, a_src, X, slope):
+    def forward(ctx, g, a_dst, a_src, X, slope, p, seed):
         heads = a_src.size(1)
         need = any(ctx.needs_input_grad[1:4])
-        out, lse = _run_gat_aggregate(g, a_dst, a_src, X, heads, slope, need)
+        out, lse = _run_gat_aggregate(g, a_dst, a_src, X, heads, slope, need, p, seed)
         if need:
-            ctx.g, ctx.heads, ctx.slope = g, heads, slope
+            ctx.g, ctx.heads, ctx.slope, ctx.p, ctx.seed = g, heads, slope, p, seed
             ctx.save_for_backward(a_dst, a_src, X, out, lse)   # node-sized, all of them
         return out
 
@@ -304,7 +360,12 @@ class GatAggregate(torch.autograd.Function):
         neg = p < 0
         torch.nn.functional.leaky_relu_(p, slope)
         p.sub_(lse.index_select(0, row)).exp_()
-        dX = _run_spmm_values(gt, p.index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
+        # attention dropout: w per (entry, head) again from the seed; dX gathers p * w, dp below becomes w * G . x
+        w = dropout_mask(g, heads, ctx.p, ctx.seed, p.dtype) if ctx.p > 0.0 else None
+        if ctx.needs_input_grad[3]:
+            dX = _run_spmm_values(gt, (p if w is None else p * w).index_select(0, perm), G, heads)
+        else:
+            dX = None
         da_dst = da_src = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             L, _ = _backend()
@@ -317,6 +378,9 @@ class GatAggregate(torch.autograd.Function):
                             X.data_ptr() + k * hd * es, X.stride(0), hd, dp[k].data_ptr(), _stream(g.device))
             ds = dp.t().contiguous()
             del dp
+            if w is not None:
+                ds.mul_(w)
+            del w
             if X.dtype in HALF_TYPES:
                 # out was rounded to 16 bits when it was stored: G . out would carry that rounding (2^-9 of sum |G . out|) into every
                 # gradient of a row.  sum_e p * dp itself, as a float32 row sum per head (the gather of da_dst below)
@@ -334,10 +398,11 @@ class GatAggregate(torch.autograd.Function):
                 da_dst = _run_spmm_values(g, ds, torch.ones((g.ncols, heads), dtype=ct, device=g.device), heads)
             if ctx.needs_input_grad[2]:   # column sums per head
                 da_src = _run_spmm_values(gt, ds.index_select(0, perm), torch.ones((g.nrows, heads), dtype=ct, device=g.device), heads)
-        return None, da_dst, da_src, dX, None
+        return None, da_dst, da_src, dX, None, None, None
 
 
-def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tensor, negative_slope: float = 0.2) -> torch.Tensor:
+def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tensor, negative_slope: float = 0.2, dropout: float = 0.0,
+                  seed=None) -> torch.Tensor:
     """the aggregation of a GAT layer, fused: with ``k = f // (h // heads)`` and e over the stored entries of row r
 
     ``out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k], negative_slope)) * X[col[e], f]``
@@ -350,7 +415,12 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
     ``[nnz, heads]`` score and probability tensors.  Differentiable in ``a_dst``, ``a_src`` and ``X``: the forward saves only
     node-sized tensors, the backward recomputes the probabilities and runs on ``spmm_values`` and ``pygim_sddmm`` (deterministic; its
     ``[nnz, heads]`` tensors are transient, a fused backward kernel is not part of this).  Runs on the device; CPU tensors are staged
-    there and the result comes back to X's device.  No double backward."""
+    there and the result comes back to X's device.  No double backward.
+
+    ``dropout`` in [0, 1): attention dropout, PyG's ``GATConv(dropout=)`` -- every coefficient is dropped with that probability after the
+    softmax, the kept ones are scaled by ``1 / (1 - dropout)``, inside the gather (see the module docstring).  ``seed``: 64 bits; ``None``
+    draws one per call from torch's default CPU generator.  0 is the call without the argument, bit for bit."""
+    dropout = _dropout_rate("gat_aggregate", dropout)
     g = EdgeGraph.of(graph)
     if X.dtype in HALF_TYPES:
         if a_dst.dtype != a_src.dtype or a_dst.dtype not in (torch.float32, X.dtype):
@@ -373,7 +443,7 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
     home = X.device
     ct = _compute_dtype(X.dtype)
     out = GatAggregate.apply(g, a_dst.to(g.device, ct).contiguous(), a_src.to(g.device, ct).contiguous(), X.to(g.device).contiguous(),
-                             float(negative_slope))
+                             float(negative_slope), dropout, _dropout_seed(seed) if dropout > 0.0 else 0)
     return out.to(home)
 
 
@@ -416,7 +486,7 @@ class HeadScores(torch.autograd.Function):
         return None, dQ, dK, None, None
 
 
-def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_lse: bool):
+def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_lse: bool, p: float = 0.0, seed: int = 0):
     """Q [nrows, h], K and V [ncols, h] contiguous on g.device, one dtype -> (out [nrows, h] in that dtype, lse [nrows, heads] in the
     compute dtype or None)"""
     L, _ = _backend()
@@ -427,19 +497,23 @@ def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_
     if g.nrows == 0:
         return out, lse
     ws = _workspace(L.sparse_attention_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
-    L.sparse_attention(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0),
-                       V.data_ptr(), V.stride(0), h, heads, scale, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
-                       _stream(g.device))
+    args = (dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0),
+            V.data_ptr(), V.stride(0), h, heads, scale, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
+            _stream(g.device))
+    if p > 0.0:
+        L.sparse_attention_dropout(*args, p, seed)
+    else:
+        L.sparse_attention(*args)
     return out, lse
 
 
 class SparseAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, Q, K, V, heads, scale):
+    def forward(ctx, g, Q, K, V, heads, scale, p, seed):
         need = any(ctx.needs_input_grad[1:4])
-        out, lse = _run_sparse_attention(g, Q, K, V, heads, scale, need)
+        out, lse = _run_sparse_attention(g, Q, K, V, heads, scale, need, p, seed)
         if need:
-            ctx.g, ctx.heads, ctx.scale = g, heads, scale
+            ctx.g, ctx.heads, ctx.scale, ctx.p, ctx.seed = g, heads, scale, p, seed
             ctx.save_for_backward(Q, K, V, out, lse)   # node-sized, all of them
         return out
 
@@ -453,10 +527,15 @@ class SparseAttention(torch.autograd.Function):
         gt, perm = g.transposed()
         # the probabilities again, from the scores and the row's log-sum-exp: [nnz, heads], transient, in the compute dtype
         p = _head_dots(g, Q, K, heads).mul_(scale).sub_(lse.index_select(0, row)).exp_()
-        dV = _run_spmm_values(gt, p.index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
+        # attention dropout: w per (entry, head) again from the seed; dV gathers p * w, dP becomes w * G . v
+        w = dropout_mask(g, heads, ctx.p, ctx.seed, p.dtype) if ctx.p > 0.0 else None
+        dV = _run_spmm_values(gt, (p if w is None else p * w).index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
         dQ = dK = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             ds = _head_dots(g, G, V, heads)   # dP
+            if w is not None:
+                ds.mul_(w)
+            del w
             if Q.dtype in HALF_TYPES:
                 # out was rounded to 16 bits when it was stored (GatAggregate.backward): sum_e p * dp itself, as a float32 row sum per head
                 delta = _run_spmm_values(g, p * ds, torch.ones((g.ncols, heads), dtype=p.dtype, device=g.device), heads)
@@ -468,10 +547,11 @@ class SparseAttention(torch.autograd.Function):
                 dQ = _run_spmm_values(g, ds, K, heads)
             if ctx.needs_input_grad[2]:
                 dK = _run_spmm_values(gt, ds.index_select(0, perm), Q, heads)
-        return None, dQ, dK, dV, None, None
+        return None, dQ, dK, dV, None, None, None, None
 
 
-def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int = 1, scale=None, fused: bool = True) -> torch.Tensor:
+def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int = 1, scale=None, fused: bool = True, dropout: float = 0.0,
+                     seed=None) -> torch.Tensor:
     """scaled dot-product attention over the stored entries: with ``hd = h // heads``, ``k = f // hd`` and e over the entries of row r
 
     ``out[r, f] = sum_e softmax_e(scale * Q[r, head k] . K[col[e], head k]) * V[col[e], f]``
@@ -484,7 +564,12 @@ def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, h
     (deterministic; its ``[nnz, heads]`` tensors are transient).  ``fused=False``: the three-pass composition -- per-head sddmm scores,
     ``edge_softmax``, ``spmm_values`` -- which heads wider than 256 features take in either case.  Differentiable in Q, K and V, each
     gradient in its operand's dtype; no double backward.  Runs on the device; CPU tensors are staged there and the result comes back
-    to Q's device."""
+    to Q's device.
+
+    ``dropout`` in [0, 1), ``seed``: attention dropout as in :func:`gat_aggregate` (PyG's ``TransformerConv(dropout=)``).  With one seed
+    ``fused=True`` and ``fused=False`` drop the same entries: the composition multiplies the ``edge_softmax`` result by
+    :func:`dropout_mask`."""
+    dropout = _dropout_rate("sparse_attention", dropout)
     g = EdgeGraph.of(graph)
     heads = int(heads)
     if Q.dtype not in FLOAT_TYPES + HALF_TYPES or K.dtype != Q.dtype or V.dtype != Q.dtype:
@@ -500,15 +585,18 @@ def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, h
     scale = hd ** -0.5 if scale is None else float(scale)
     home = Q.device
     q, k, v = (t.to(g.device).contiguous() for t in (Q, K, V))
+    seed = _dropout_seed(seed) if dropout > 0.0 else 0
     if fused and hd <= SA_MAX_HEAD:
-        out = SparseAttention.apply(g, q, k, v, heads, scale)
+        out = SparseAttention.apply(g, q, k, v, heads, scale, dropout, seed)
     else:
         p = EdgeSoftmax.apply(g, HeadScores.apply(g, q, k, heads, scale), heads)
+        if dropout > 0.0:
+            p = p * dropout_mask(g, heads, dropout, seed, p.dtype)
         out = SpmmValues.apply(g, p, v, heads)
     return out.to(home)
 
 
-def _run_gatv2_aggregate(g: EdgeGraph, x_dst, x_src, att, heads: int, slope: float, want_lse: bool):
+def _run_gatv2_aggregate(g: EdgeGraph, x_dst, x_src, att, heads: int, slope: float, want_lse: bool, p: float = 0.0, seed: int = 0):
     """x_dst [nrows, h] and x_src [ncols, h] contiguous on g.device, one dtype; att [h] in the compute dtype -> (out [nrows, h] in the
     feature dtype, lse [nrows, heads] in the compute dtype or None)"""
     L, _ = _backend()
@@ -519,15 +607,21 @@ def _run_gatv2_aggregate(g: EdgeGraph, x_dst, x_src, att, heads: int, slope: flo
     if g.nrows == 0:
         return out, lse
     ws = _workspace(L.gatv2_aggregate_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
-    L.gatv2_aggregate(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, x_dst.data_ptr(), x_dst.stride(0), x_src.data_ptr(),
-                      x_src.stride(0), att.data_ptr(), h, heads, slope, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
-                      _stream(g.device))
+    args = (dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, x_dst.data_ptr(), x_dst.stride(0), x_src.data_ptr(),
+            x_src.stride(0), att.data_ptr(), h, heads, slope, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
+            _stream(g.device))
+    if p > 0.0:
+        L.gatv2_aggregate_dropout(*args, p, seed)
+    else:
+        L.gatv2_aggregate(*args)
     return out, lse
 
 
-def _run_gatv2_backward(g: EdgeGraph, transposed: bool, own, oth, att, heads: int, slope: float, G, lse, delta, want_datt: bool):
+def _run_gatv2_backward(g: EdgeGraph, transposed: bool, own, oth, att, heads: int, slope: float, G, lse, delta, want_datt: bool, p: float = 0.0,
+                        seed: int = 0, entry_ids=None):
     """one pygim_gatv2_backward call on ``g`` (the graph of A, or of A^T when ``transposed``) -> (d_own [g.nrows, h] in the feature dtype,
-    datt [h] in the compute dtype or None)"""
+    datt [h] in the compute dtype or None).  p > 0: the forward ran with attention dropout (p, seed); entry_ids is the int32 index in A of
+    every entry of ``g`` (None: ``g`` is the graph of A)"""
     L, _ = _backend()
     dt = _gather_code(own.dtype)
     h = own.size(1)
@@ -536,19 +630,23 @@ def _run_gatv2_backward(g: EdgeGraph, transposed: bool, own, oth, att, heads: in
     if g.nrows == 0:
         return d_own, None if datt is None else datt.zero_()
     ws = _workspace(L.gatv2_backward_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
-    L.gatv2_backward(dt, 1 if transposed else 0, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, own.data_ptr(), own.stride(0), oth.data_ptr(),
-                     oth.stride(0), att.data_ptr(), h, heads, slope, G.data_ptr(), G.stride(0), lse.data_ptr(), delta.data_ptr(), d_own.data_ptr(), h,
-                     datt.data_ptr() if want_datt else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    args = (dt, 1 if transposed else 0, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, own.data_ptr(), own.stride(0), oth.data_ptr(),
+            oth.stride(0), att.data_ptr(), h, heads, slope, G.data_ptr(), G.stride(0), lse.data_ptr(), delta.data_ptr(), d_own.data_ptr(), h,
+            datt.data_ptr() if want_datt else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
+    if p > 0.0:
+        L.gatv2_backward_dropout(*args, 0 if entry_ids is None else entry_ids.data_ptr(), p, seed)
+    else:
+        L.gatv2_backward(*args)
     return d_own, datt
 
 
 class GatV2Aggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, x_dst, x_src, att, heads, slope):
+    def forward(ctx, g, x_dst, x_src, att, heads, slope, p, seed):
         need = any(ctx.needs_input_grad[1:4])
-        out, lse = _run_gatv2_aggregate(g, x_dst, x_src, att, heads, slope, need)
+        out, lse = _run_gatv2_aggregate(g, x_dst, x_src, att, heads, slope, need, p, seed)
         if need:
-            ctx.g, ctx.heads, ctx.slope = g, heads, slope
+            ctx.g, ctx.heads, ctx.slope, ctx.p, ctx.seed = g, heads, slope, p, seed
             ctx.save_for_backward(x_dst, x_src, att, out, lse)   # node-sized, all of them
         return out
 
@@ -562,17 +660,18 @@ class GatV2Aggregate(torch.autograd.Function):
         delta = (G.to(att.dtype) * out.to(att.dtype)).view(g.nrows, heads, h // heads).sum(-1).contiguous()
         dx_dst = dx_src = datt = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
-            dx_dst, datt = _run_gatv2_backward(g, False, x_dst, x_src, att, heads, slope, G, lse, delta, ctx.needs_input_grad[3])
+            dx_dst, datt = _run_gatv2_backward(g, False, x_dst, x_src, att, heads, slope, G, lse, delta, ctx.needs_input_grad[3], ctx.p, ctx.seed)
             if not ctx.needs_input_grad[1]:
                 dx_dst = None
         if ctx.needs_input_grad[2]:
-            gt, _ = g.transposed()   # the permutation is not needed: nothing per entry is stored
-            dx_src, _ = _run_gatv2_backward(gt, True, x_src, x_dst, att, heads, slope, G, lse, delta, False)
-        return None, dx_dst, dx_src, datt, None, None
+            gt, _ = g.transposed()   # the permutation is needed only by attention dropout: the mask is a function of the entry's index in A
+            dx_src, _ = _run_gatv2_backward(gt, True, x_src, x_dst, att, heads, slope, G, lse, delta, False, ctx.p, ctx.seed,
+                                            g.entry_ids_t() if ctx.p > 0.0 else None)
+        return None, dx_dst, dx_src, datt, None, None, None, None
 
 
 def gatv2_aggregate(graph, x_dst: torch.Tensor, x_src: torch.Tensor, att: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
-                    fused: bool = True) -> torch.Tensor:
+                    fused: bool = True, dropout: float = 0.0, seed=None) -> torch.Tensor:
     """the aggregation of a GATv2 layer (Brody et al.; PyG's GATv2Conv): with ``hd = h // heads``, ``k = f // hd`` and e over the entries of row r
 
     ``s[e, k] = sum_{f in head k} att[f] * leaky_relu(x_dst[r, f] + x_src[col[e], f], negative_slope)``
@@ -590,7 +689,12 @@ def gatv2_aggregate(graph, x_dst: torch.Tensor, x_src: torch.Tensor, att: torch.
     ``fused=False``, and heads wider than 256 features in either case: PyG's composition -- ``z = x_dst[row] + x_src[col]``, the scores in
     torch, ``edge_softmax``, ``spmm_values`` -- which materialises ``[nnz, h]`` tensors and keeps them for the backward.
     Differentiable in x_dst, x_src and att, each gradient in its operand's dtype; no double backward.  Runs on the device; CPU tensors are
-    staged there and the result comes back to x_src's device."""
+    staged there and the result comes back to x_src's device.
+
+    ``dropout`` in [0, 1), ``seed``: attention dropout as in :func:`gat_aggregate` (PyG's ``GATv2Conv(dropout=)``), in the forward gather
+    and in both backward gathers (pygim_gatv2_backward_dropout; the transposed one reads the entry's index in A from an int32 copy of
+    ``perm`` cached on the graph).  ``fused=False`` multiplies the ``edge_softmax`` result by :func:`dropout_mask`: the same entries."""
+    dropout = _dropout_rate("gatv2_aggregate", dropout)
     g = EdgeGraph.of(graph)
     heads = int(heads)
     if x_src.dtype not in FLOAT_TYPES + HALF_TYPES or x_dst.dtype != x_src.dtype:
@@ -612,11 +716,15 @@ def gatv2_aggregate(graph, x_dst: torch.Tensor, x_src: torch.Tensor, att: torch.
     ct = _compute_dtype(x_src.dtype)
     xd, xs = x_dst.to(g.device).contiguous(), x_src.to(g.device).contiguous()
     a = att.to(g.device, ct).reshape(h).contiguous()
+    seed = _dropout_seed(seed) if dropout > 0.0 else 0
     if fused and hd <= SA_MAX_HEAD:
-        out = GatV2Aggregate.apply(g, xd, xs, a, heads, slope)
+        out = GatV2Aggregate.apply(g, xd, xs, a, heads, slope, dropout, seed)
     else:
         row, col = g.row.long(), g.col.long()
         z = xd.to(ct).index_select(0, row) + xs.to(ct).index_select(0, col)   # [nnz, h]
         s = (torch.nn.functional.leaky_relu(z, slope) * a).view(g.nnz, heads, hd).sum(-1)
-        out = SpmmValues.apply(g, EdgeSoftmax.apply(g, s.contiguous(), heads), xs, heads)
+        pr = EdgeSoftmax.apply(g, s.contiguous(), heads)
+        if dropout > 0.0:
+            pr = pr * dropout_mask(g, heads, dropout, seed, pr.dtype)
+        out = SpmmValues.apply(g, pr, xs, heads)
     return out.to(home)

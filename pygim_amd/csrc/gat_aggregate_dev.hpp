@@ -27,6 +27,7 @@
 
 #include <cstdint>
 
+#include "attn_dropout_dev.hpp"
 #include "edge_softmax_dev.hpp"
 #include "row_gather_dev.hpp"
 
@@ -52,11 +53,13 @@ inline uint64_t gat_workspace_bytes(uint64_t nnz, uint64_t h, uint64_t heads, si
 // lse may be null.  ws: accumulator slots, ws_stat: the (m, l) slots.
 // S is the storage type of X and out, T the type of a_dst, a_src, lse, (m, l, acc) and the slots (S = T, or a 16-bit S with T = float:
 // an X piece is widened as it is folded, acc / l is rounded once where a finished row is stored).
-template <typename T, typename S, int VEC, int NV, bool WHOLE>
+// DROP: attention dropout (attn_dropout_dev.hpp).  A probability goes into l unchanged and into the accumulate as p * w, w = 1 / (1 - rate) or
+// 0 from the mask of (entry index base + kk, the piece's head hv[v]); m, l, lse and everything else are untouched.  dr is read only then.
+template <typename T, typename S, int VEC, int NV, bool WHOLE, bool DROP = false>
 __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                     const T *__restrict__ a_dst, const T *__restrict__ a_src, uint32_t heads, T slope,
                                                     const S *__restrict__ X, uint64_t ldx, uint32_t h, uint32_t L, S *__restrict__ out, uint64_t ldo,
-                                                    T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat) {
+                                                    T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr) {
     using V = typename SdVec<S, VEC>::type;
     constexpr int U = NV == 1 ? RG_U : RG_U / 2;
     if constexpr (WHOLE) L = 64;
@@ -187,8 +190,10 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
 #pragma unroll
                     for (int u = 0; u < U; u++)
                         if (ok[u] && fok[v]) {
-                            const T p = es_exp(s[u][v] - M);
+                            T p = es_exp(s[u][v] - M);
                             l[v] = l[v] + p;
+                            if constexpr (DROP)
+                                p = attn_dropout_keep(base + k0 + (uint32_t)u * R + grp, hv[v], dr.seed_lo, dr.seed_hi, dr.thr) ? p * dr.keep_w : T(0);
 #pragma unroll
                             for (int i = 0; i < VEC; i++) acc[v][i] = acc[v][i] + p * T(rg_get<S, VEC>(x[u][v], i));
                         }
@@ -252,27 +257,29 @@ __global__ __launch_bounds__(256) void k_gat_empty(const uint32_t *__restrict__ 
         for (uint32_t k = lane; k < heads; k += 64) lse[row * heads + k] = T(0);
 }
 
-template <typename T, typename S, int VEC>
+template <typename T, typename S, int VEC, bool DROP>
 inline void launch_gat_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, const LaunchShape &g,
-                                hipStream_t st) {
+                                const AttnDrop<T> &dr, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
     if (g.L < 64) {
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, g.L,
-                           out, ldo, lse, ws, ws_stat);
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false, DROP>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, g.L,
+                           out, ldo, lse, ws, ws_stat, dr);
     } else if (g.npl == 1) {
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, true>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
-                           out, ldo, lse, ws, ws_stat);
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, true, DROP>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
+                           out, ldo, lse, ws, ws_stat, dr);
     } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
-                           slope, X, ldx, h, 64u, out, ldo, lse, ws, ws_stat);
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true, DROP>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
+                           slope, X, ldx, h, 64u, out, ldo, lse, ws, ws_stat, dr);
     }
 }
 
 // 16-byte pieces (of the storage type) under the conditions of launch_row_gather: aligned rows of X and out, and no piece across two heads
-template <typename T, typename S = T>
+// DROP: with attention dropout of (rate, seed) = dr; without it dr is not read
+template <typename T, typename S = T, bool DROP = false>
 inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
-                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, void *workspace, hipStream_t st) {
+                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, void *workspace, hipStream_t st,
+                                 const AttnDrop<T> &dr = AttnDrop<T>()) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
@@ -280,8 +287,8 @@ inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind,
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
     const bool aligned = ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
     const LaunchShape g = row_gather_shape(h, h / heads, V, aligned);   // the walker's layout
-    if (g.vec > 1) launch_gat_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, st);
-    else launch_gat_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, st);
+    if (g.vec > 1) launch_gat_gather_v<T, S, (int)V, DROP>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, st);
+    else launch_gat_gather_v<T, S, 1, DROP>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

@@ -58,12 +58,13 @@ __device__ inline T gv2_score_part(const T (&att)[NP][VEC], const typename SdVec
 }
 
 // S is the storage type of x_dst, x_src and out, T the type of att, z, the scores, lse, (m, l, acc) and the slots (S = T, or a 16-bit S
-// with T = float).  LH, L, head0: as in k_sa_gather.
-template <typename T, typename S, int VEC, int NP>
+// with T = float).  LH, L, head0, DROP and dr: as in k_sa_gather.
+template <typename T, typename S, int VEC, int NP, bool DROP = false>
 __global__ __launch_bounds__(256) void k_gatv2_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                       const S *__restrict__ Xd, uint64_t ldxd, const S *__restrict__ Xs, uint64_t ldxs,
                                                       const T *__restrict__ att, uint32_t h, uint32_t heads, uint32_t head0, T slope, uint32_t LH, uint32_t L,
-                                                      S *__restrict__ out, uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat) {
+                                                      S *__restrict__ out, uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat,
+                                                      AttnDrop<T> dr) {
     using V = typename SdVec<S, VEC>::type;
     constexpr int U = RG_U / NP;
     const uint32_t R = 64 / L;
@@ -198,8 +199,10 @@ __global__ __launch_bounds__(256) void k_gatv2_gather(const uint32_t *__restrict
 #pragma unroll
                 for (int u = 0; u < U; u++)
                     if (ok[u]) {
-                        const T pr = es_exp(s[u] - M);
+                        T pr = es_exp(s[u] - M);
                         l = l + pr;
+                        if constexpr (DROP)
+                            pr = attn_dropout_keep(base + k0 + (uint32_t)u * R + grp, head, dr.seed_lo, dr.seed_hi, dr.thr) ? pr * dr.keep_w : T(0);
 #pragma unroll
                         for (int p = 0; p < NP; p++)
 #pragma unroll
@@ -222,12 +225,16 @@ __global__ __launch_bounds__(256) void k_gatv2_gather(const uint32_t *__restrict
 // own / oth: the walked CSR's row operand and the gathered one (x_dst / x_src on the CSR of A, x_src / x_dst on the CSR of A^T).  G, lse
 // [., heads] and delta [., heads] belong to the rows of A: the own row when !TRANSPOSED, the gathered row otherwise.  d_own: the gradient
 // of own.  ws: two slots of h per run; ws_datt (!TRANSPOSED): h per run.  S stores own, oth, G and d_own; everything else is T.
-template <typename T, typename S, int VEC, int NP, bool TRANSPOSED>
+// DROP: the forward ran with attention dropout dr: dp = w * sum G x_src, and the transposed direction accumulates pr * w * G + t.  w is the
+// mask of (entry index IN A, head): entry_ids[walked index] -- the perm of the transposed CSR, loaded per lane beside colind and
+// broadcast like my_col -- or the walked index itself when entry_ids is null.
+template <typename T, typename S, int VEC, int NP, bool TRANSPOSED, bool DROP = false>
 __global__ __launch_bounds__(256) void k_gatv2_grad(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                     const S *__restrict__ own, uint64_t ld_own, const S *__restrict__ oth, uint64_t ld_oth,
                                                     const T *__restrict__ att, uint32_t h, uint32_t heads, uint32_t head0, T slope, const S *__restrict__ G,
                                                     uint64_t ldg, const T *__restrict__ lse, const T *__restrict__ delta, uint32_t LH, uint32_t L,
-                                                    S *__restrict__ d_own, uint64_t ldd, T *__restrict__ ws, T *__restrict__ ws_datt) {
+                                                    S *__restrict__ d_own, uint64_t ldd, T *__restrict__ ws, T *__restrict__ ws_datt,
+                                                    const int32_t *__restrict__ entry_ids, AttnDrop<T> dr) {
     using V = typename SdVec<S, VEC>::type;
     // entries in flight: k_sa_gather's RG_U / NP, at most 32 gathered elements per lane (8-element pieces of a 16-bit type are widened to float32
     // for two sums and an accumulate: more of them in flight cost the kernel its second wave per SIMD), half when TRANSPOSED gathers two rows
@@ -291,6 +298,9 @@ __global__ __launch_bounds__(256) void k_gatv2_grad(const uint32_t *__restrict__
         const uint32_t my_e = base + lane;
         const bool valid = lane < n;
         const uint32_t my_col = valid ? colind[my_e] : 0u;
+        uint32_t my_id = my_e;   // DROP: the entry's index in A
+        if constexpr (DROP)
+            if (entry_ids) my_id = valid ? (uint32_t)entry_ids[my_e] : 0u;
         uint32_t my_row = row_cur;
         bool my_end = false;
         if (valid) {
@@ -322,11 +332,13 @@ __global__ __launch_bounds__(256) void k_gatv2_grad(const uint32_t *__restrict__
                 V x[U][NP], gj[TRANSPOSED ? U : 1][NP];
                 T s[U], dp[U], ls[U], dl[U];
                 bool ok[U];
+                uint32_t id[DROP ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     const uint32_t kk = k0 + (uint32_t)u * R + grp;
                     ok[u] = kk <= last;
                     const uint32_t col = rg_take32<false>(my_col, ok[u] ? kk : pos);
+                    if constexpr (DROP) id[u] = rg_take32<false>(my_id, ok[u] ? kk : pos);
                     const S *xr = oth + (uint64_t)col * ld_oth;
                     ls[u] = ls_row;
                     dl[u] = dl_row;
@@ -370,6 +382,12 @@ __global__ __launch_bounds__(256) void k_gatv2_grad(const uint32_t *__restrict__
                 for (int u = 0; u < U; u++)
                     if (ok[u]) {
                         const T pr = es_exp(s[u] - ls[u]);
+                        T pw = pr;   // pr * w
+                        if constexpr (DROP) {
+                            const T w = attn_dropout_keep(id[u], head, dr.seed_lo, dr.seed_hi, dr.thr) ? dr.keep_w : T(0);
+                            dp[u] = dp[u] * w;
+                            pw = pr * w;
+                        }
                         const T ds = pr * (dp[u] - dl[u]);
 #pragma unroll
                         for (int p = 0; p < NP; p++)
@@ -378,7 +396,7 @@ __global__ __launch_bounds__(256) void k_gatv2_grad(const uint32_t *__restrict__
                                 const T z = T(rg_get<S, VEC>(o[p], i)) + T(rg_get<S, VEC>(x[u][p], i));
                                 const bool pos_z = z > T(0);
                                 const T t = ds * a[p][i] * (pos_z ? T(1) : slope);
-                                if constexpr (TRANSPOSED) acc[p][i] = acc[p][i] + (pr * T(rg_get<S, VEC>(gj[u][p], i)) + t);
+                                if constexpr (TRANSPOSED) acc[p][i] = acc[p][i] + (pw * T(rg_get<S, VEC>(gj[u][p], i)) + t);
                                 else {
                                     acc[p][i] = acc[p][i] + t;
                                     dacc[p][i] = dacc[p][i] + ds * (pos_z ? z : slope * z);
@@ -424,15 +442,15 @@ __global__ __launch_bounds__(256) void k_gatv2_datt_reduce(const T *__restrict__
 }
 
 // the lane layout is head_gather_shape's (sparse_attention_dev.hpp)
-template <typename T, typename S, int VEC>
+template <typename T, typename S, int VEC, bool DROP>
 inline void launch_gatv2_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Xd, uint64_t ldxd, const S *Xs,
                                   uint64_t ldxs, const T *att, uint32_t h, uint32_t heads, T slope, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat,
-                                  const LaunchShape &g, hipStream_t st) {
+                                  const LaunchShape &g, const AttnDrop<T> &dr, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
 #define PYGIM_GV2_LAUNCH(NP)                                                                                                                          \
     for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                         \
-    hipLaunchKernelGGL((k_gatv2_gather<T, S, VEC, NP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
-                       rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, c0 * g.per, slope, g.LH, g.L, out, ldo, lse, ws, ws_stat)
+    hipLaunchKernelGGL((k_gatv2_gather<T, S, VEC, NP, DROP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
+                       rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, c0 * g.per, slope, g.LH, g.L, out, ldo, lse, ws, ws_stat, dr)
     constexpr uint32_t MAX_NP = (GV2_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);   // only the piece counts a head of GV2_MAX_HEAD can need
     if (g.npl == 1) PYGIM_GV2_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
@@ -444,10 +462,10 @@ inline void launch_gatv2_gather_v(const uint32_t *rowptr, const uint32_t *colind
 
 // 16-byte pieces (of the storage type) when a head's features fill whole pieces and every row of x_dst, x_src and out starts 16-byte
 // aligned; else one element per lane.  The caller has checked h / heads <= GV2_MAX_HEAD.  The workspace is gat_aggregate's.
-template <typename T, typename S = T>
+template <typename T, typename S = T, bool DROP = false>
 inline void launch_gatv2_aggregate(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Xd, uint64_t ldxd, const S *Xs,
                                    uint64_t ldxs, const T *att, uint32_t h, uint32_t heads, T slope, S *out, uint64_t ldo, T *lse, void *workspace,
-                                   hipStream_t st) {
+                                   hipStream_t st, const AttnDrop<T> &dr = AttnDrop<T>()) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
@@ -456,8 +474,8 @@ inline void launch_gatv2_aggregate(const uint32_t *rowptr, const uint32_t *colin
     const bool aligned = ldxd % V == 0 && ldxs % V == 0 && ldo % V == 0 && (uintptr_t)Xd % 16 == 0 && (uintptr_t)Xs % 16 == 0 &&
                          (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
     const LaunchShape g = head_gather_shape(h, heads, V, aligned);
-    if (g.vec > 1) launch_gatv2_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, st);
-    else launch_gatv2_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, st);
+    if (g.vec > 1) launch_gatv2_gather_v<T, S, (int)V, DROP>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, dr, st);
+    else launch_gatv2_gather_v<T, S, 1, DROP>(rowptr, colind, nrows, nnz, Xd, ldxd, Xs, ldxs, att, h, heads, slope, out, ldo, lse, ws, ws_stat, g, dr, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);
@@ -473,16 +491,17 @@ inline uint64_t gatv2_backward_workspace_bytes(uint64_t nnz, uint64_t h, size_t 
     return gatv2_datt2_offset(nnz, h, elem) + (row_gather_runs(nnz) + GV2_RED - 1) / GV2_RED * h * elem;
 }
 
-template <typename T, typename S, int VEC, bool TRANSPOSED>
+template <typename T, typename S, int VEC, bool TRANSPOSED, bool DROP>
 inline void launch_gatv2_grad_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *own, uint64_t ld_own, const S *oth,
                                 uint64_t ld_oth, const T *att, uint32_t h, uint32_t heads, T slope, const S *G, uint64_t ldg, const T *lse, const T *delta,
-                                S *d_own, uint64_t ldd, T *ws, T *ws_datt, const LaunchShape &g, hipStream_t st) {
+                                S *d_own, uint64_t ldd, T *ws, T *ws_datt, const LaunchShape &g, const int32_t *entry_ids, const AttnDrop<T> &dr,
+                                hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
 #define PYGIM_GV2_LAUNCH(NP)                                                                                                                           \
     for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                          \
-    hipLaunchKernelGGL((k_gatv2_grad<T, S, VEC, NP, TRANSPOSED>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
+    hipLaunchKernelGGL((k_gatv2_grad<T, S, VEC, NP, TRANSPOSED, DROP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, \
                        rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, c0 * g.per, slope, G, ldg, lse, delta, g.LH, g.L, d_own, ldd, ws,   \
-                       ws_datt)
+                       ws_datt, entry_ids, dr)
     constexpr uint32_t MAX_NP = (GV2_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);
     if (g.npl == 1) PYGIM_GV2_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
@@ -493,10 +512,12 @@ inline void launch_gatv2_grad_v(const uint32_t *rowptr, const uint32_t *colind, 
 }
 
 // one direction of the backward (see k_gatv2_grad).  datt: null when TRANSPOSED; when !TRANSPOSED and null, the reduction is skipped.
-template <typename T, typename S, bool TRANSPOSED>
+// DROP: the forward's attention dropout dr, entry_ids: the index in A of every walked entry (null: the walked index)
+template <typename T, typename S, bool TRANSPOSED, bool DROP = false>
 inline void launch_gatv2_backward(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *own, uint64_t ld_own, const S *oth,
                                   uint64_t ld_oth, const T *att, uint32_t h, uint32_t heads, T slope, const S *G, uint64_t ldg, const T *lse, const T *delta,
-                                  S *d_own, uint64_t ldd, T *datt, void *workspace, hipStream_t st) {
+                                  S *d_own, uint64_t ldd, T *datt, void *workspace, hipStream_t st, const int32_t *entry_ids = nullptr,
+                                  const AttnDrop<T> &dr = AttnDrop<T>()) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_row_gather_empty<S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, d_own, ldd, nullptr);
     const uint64_t runs = row_gather_runs(nnz);
@@ -508,11 +529,11 @@ inline void launch_gatv2_backward(const uint32_t *rowptr, const uint32_t *colind
                              (uintptr_t)G % 16 == 0 && (uintptr_t)d_own % 16 == 0 && (uintptr_t)ws % 16 == 0;
         const LaunchShape g = head_gather_shape(h, heads, V, aligned);
         if (g.vec > 1)
-            launch_gatv2_grad_v<T, S, (int)V, TRANSPOSED>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta, d_own,
-                                                          ldd, ws, part, g, st);
+            launch_gatv2_grad_v<T, S, (int)V, TRANSPOSED, DROP>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta,
+                                                                d_own, ldd, ws, part, g, entry_ids, dr, st);
         else
-            launch_gatv2_grad_v<T, S, 1, TRANSPOSED>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta, d_own, ldd, ws,
-                                                     part, g, st);
+            launch_gatv2_grad_v<T, S, 1, TRANSPOSED, DROP>(rowptr, colind, nrows, nnz, own, ld_own, oth, ld_oth, att, h, heads, slope, G, ldg, lse, delta, d_own, ldd,
+                                                           ws, part, g, entry_ids, dr, st);
         if (runs > 1)
             hipLaunchKernelGGL((k_row_gather_fixup<T, S, FoldSum<false>>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, ws, nullptr,
                                d_own, ldd, nullptr);

@@ -714,9 +714,14 @@ int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int
     return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
 }
 
-int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
-                        int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
-                        int64_t workspace_bytes, void *stream) {
+// attention dropout: the rate of the *_dropout entry points (0 <= p < 1; NaN fails the first comparison)
+static bool bad_dropout(double p) { return !(p >= 0.0 && p < 1.0); }
+
+// p = 0 launches the instantiation without dropout: the base entry point and its bits
+static int gat_aggregate_call(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
+                              int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse,
+                              void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: the dropout rate must lie in [0, 1)");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: heads must divide h");
@@ -727,12 +732,31 @@ int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const i
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        launch_gat_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
-                                   (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace,
-                                   (hipStream_t)stream);
+        if (p > 0.0)
+            launch_gat_aggregate<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst,
+                                             (const T *)a_src, (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out,
+                                             (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, attn_dropout_args<T>(p, seed));
+        else
+            launch_gat_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst, (const T *)a_src,
+                                       (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace,
+                                       (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int pygim_gat_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
+                        int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+    return gat_aggregate_call(dtype, nrows, rowptr, colind, nnz, a_dst, a_src, heads, negative_slope, X, ldx, h, out, ldo, lse, workspace, workspace_bytes,
+                              stream, 0.0, 0);
+}
+
+int pygim_gat_aggregate_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
+                                int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse,
+                                void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    return gat_aggregate_call(dtype, nrows, rowptr, colind, nnz, a_dst, a_src, heads, negative_slope, X, ldx, h, out, ldo, lse, workspace, workspace_bytes,
+                              stream, p, seed);
 }
 
 int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
@@ -741,9 +765,10 @@ int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, 
     return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
 }
 
-int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq, const void *K,
-                           int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo, void *lse,
-                           void *workspace, int64_t workspace_bytes, void *stream) {
+static int sparse_attention_call(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq,
+                                 const void *K, int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
+                                 void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "sparse_attention: the dropout rate must lie in [0, 1)");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "sparse_attention: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "sparse_attention: heads must divide h");
@@ -756,12 +781,31 @@ int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, cons
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        launch_sparse_attention<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
-                                      (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
-                                      (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
+        if (p > 0.0)
+            launch_sparse_attention<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
+                                                (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
+                                                (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, attn_dropout_args<T>(p, seed));
+        else
+            launch_sparse_attention<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
+                                          (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
+                                          (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int pygim_sparse_attention(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq, const void *K,
+                           int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo, void *lse,
+                           void *workspace, int64_t workspace_bytes, void *stream) {
+    return sparse_attention_call(dtype, nrows, rowptr, colind, nnz, Q, ldq, K, ldk, V, ldv, h, heads, scale, out, ldo, lse, workspace, workspace_bytes, stream,
+                                 0.0, 0);
+}
+
+int pygim_sparse_attention_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq,
+                                   const void *K, int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
+                                   void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    return sparse_attention_call(dtype, nrows, rowptr, colind, nnz, Q, ldq, K, ldk, V, ldv, h, heads, scale, out, ldo, lse, workspace, workspace_bytes, stream,
+                                 p, seed);
 }
 
 int64_t pygim_gatv2_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
@@ -770,9 +814,10 @@ int64_t pygim_gatv2_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, i
     return (int64_t)gat_workspace_bytes((uint64_t)nnz, (uint64_t)h, (uint64_t)heads, gather_compute_size(dtype));
 }
 
-int pygim_gatv2_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_dst, int64_t ld_dst,
-                          const void *x_src, int64_t ld_src, const void *att, int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo,
-                          void *lse, void *workspace, int64_t workspace_bytes, void *stream) {
+static int gatv2_aggregate_call(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_dst, int64_t ld_dst,
+                                const void *x_src, int64_t ld_src, const void *att, int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo,
+                                void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: the dropout rate must lie in [0, 1)");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gatv2_aggregate: heads must divide h");
@@ -785,12 +830,32 @@ int pygim_gatv2_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        launch_gatv2_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_dst, (uint64_t)ld_dst,
-                                     (const S *)x_src, (uint64_t)ld_src, (const T *)att, (uint32_t)h, (uint32_t)heads, (T)negative_slope, (S *)out,
-                                     (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
+        if (p > 0.0)
+            launch_gatv2_aggregate<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_dst,
+                                               (uint64_t)ld_dst, (const S *)x_src, (uint64_t)ld_src, (const T *)att, (uint32_t)h, (uint32_t)heads,
+                                               (T)negative_slope, (S *)out, (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream,
+                                               attn_dropout_args<T>(p, seed));
+        else
+            launch_gatv2_aggregate<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_dst, (uint64_t)ld_dst,
+                                         (const S *)x_src, (uint64_t)ld_src, (const T *)att, (uint32_t)h, (uint32_t)heads, (T)negative_slope, (S *)out,
+                                         (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int pygim_gatv2_aggregate(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_dst, int64_t ld_dst,
+                          const void *x_src, int64_t ld_src, const void *att, int64_t h, int64_t heads, double negative_slope, void *out, int64_t ldo,
+                          void *lse, void *workspace, int64_t workspace_bytes, void *stream) {
+    return gatv2_aggregate_call(dtype, nrows, rowptr, colind, nnz, x_dst, ld_dst, x_src, ld_src, att, h, heads, negative_slope, out, ldo, lse, workspace,
+                                workspace_bytes, stream, 0.0, 0);
+}
+
+int pygim_gatv2_aggregate_dropout(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_dst, int64_t ld_dst,
+                                  const void *x_src, int64_t ld_src, const void *att, int64_t h, int64_t heads, double negative_slope, void *out,
+                                  int64_t ldo, void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+    return gatv2_aggregate_call(dtype, nrows, rowptr, colind, nnz, x_dst, ld_dst, x_src, ld_src, att, h, heads, negative_slope, out, ldo, lse, workspace,
+                                workspace_bytes, stream, p, seed);
 }
 
 int64_t pygim_gatv2_backward_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
@@ -799,10 +864,11 @@ int64_t pygim_gatv2_backward_workspace(int dtype, int64_t nrows, int64_t nnz, in
     return (int64_t)gatv2_backward_workspace_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
 }
 
-int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_own,
-                         int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att, int64_t h, int64_t heads, double negative_slope, const void *G,
-                         int64_t ldg, const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace, int64_t workspace_bytes,
-                         void *stream) {
+static int gatv2_backward_call(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_own,
+                               int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att, int64_t h, int64_t heads, double negative_slope,
+                               const void *G, int64_t ldg, const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace,
+                               int64_t workspace_bytes, void *stream, const int32_t *entry_ids, double p, uint64_t seed) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "gatv2_backward: the dropout rate must lie in [0, 1)");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gatv2_backward: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gatv2_backward: heads must divide h");
@@ -811,13 +877,23 @@ int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t
     if (int rc = check_csr_call("gatv2_backward", "rowptr / colind / x_own / x_oth / att / G / lse / delta / d_own", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll,
                                 ld_own < ld_oth ? ld_own : ld_oth, ldg < ldd ? ldg : ldd,
                                 {{rowptr, true}, {d_own, nrows > 0}, {datt, true, true}, {colind, nnz > 0}, {x_own, nnz > 0}, {x_oth, nnz > 0},
-                                 {att, nnz > 0}, {G, nnz > 0}, {lse, nnz > 0}, {delta, nnz > 0}},
+                                 {att, nnz > 0}, {G, nnz > 0}, {lse, nnz > 0}, {delta, nnz > 0}, {entry_ids, nnz > 0 && p > 0.0, true}},
                                 pygim_gatv2_backward_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        if (transposed)
+        if (p > 0.0 && transposed)
+            launch_gatv2_backward<T, S, true, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_own,
+                                                    (uint64_t)ld_own, (const S *)x_oth, (uint64_t)ld_oth, (const T *)att, (uint32_t)h, (uint32_t)heads,
+                                                    (T)negative_slope, (const S *)G, (uint64_t)ldg, (const T *)lse, (const T *)delta, (S *)d_own,
+                                                    (uint64_t)ldd, nullptr, workspace, (hipStream_t)stream, entry_ids, attn_dropout_args<T>(p, seed));
+        else if (p > 0.0)
+            launch_gatv2_backward<T, S, false, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_own,
+                                                     (uint64_t)ld_own, (const S *)x_oth, (uint64_t)ld_oth, (const T *)att, (uint32_t)h, (uint32_t)heads,
+                                                     (T)negative_slope, (const S *)G, (uint64_t)ldg, (const T *)lse, (const T *)delta, (S *)d_own,
+                                                     (uint64_t)ldd, (T *)datt, workspace, (hipStream_t)stream, entry_ids, attn_dropout_args<T>(p, seed));
+        else if (transposed)
             launch_gatv2_backward<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)x_own,
                                               (uint64_t)ld_own, (const S *)x_oth, (uint64_t)ld_oth, (const T *)att, (uint32_t)h, (uint32_t)heads,
                                               (T)negative_slope, (const S *)G, (uint64_t)ldg, (const T *)lse, (const T *)delta, (S *)d_own, (uint64_t)ldd,
@@ -829,6 +905,51 @@ int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t
                                                (T *)datt, workspace, (hipStream_t)stream);
     });
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pygim_gatv2_backward(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_own,
+                         int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att, int64_t h, int64_t heads, double negative_slope, const void *G,
+                         int64_t ldg, const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace, int64_t workspace_bytes,
+                         void *stream) {
+    return gatv2_backward_call(dtype, transposed, nrows, rowptr, colind, nnz, x_own, ld_own, x_oth, ld_oth, att, h, heads, negative_slope, G, ldg, lse, delta,
+                               d_own, ldd, datt, workspace, workspace_bytes, stream, nullptr, 0.0, 0);
+}
+
+int pygim_gatv2_backward_dropout(int dtype, int transposed, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *x_own,
+                                 int64_t ld_own, const void *x_oth, int64_t ld_oth, const void *att, int64_t h, int64_t heads, double negative_slope,
+                                 const void *G, int64_t ldg, const void *lse, const void *delta, void *d_own, int64_t ldd, void *datt, void *workspace,
+                                 int64_t workspace_bytes, void *stream, const int32_t *entry_ids, double p, uint64_t seed) {
+    return gatv2_backward_call(dtype, transposed, nrows, rowptr, colind, nnz, x_own, ld_own, x_oth, ld_oth, att, h, heads, negative_slope, G, ldg, lse, delta,
+                               d_own, ldd, datt, workspace, workspace_bytes, stream, entry_ids, p, seed);
+}
+
+int pygim_attention_dropout_mask(int dtype, int64_t nnz, int64_t heads, const int32_t *entry_ids, double p, uint64_t seed, void *mask, void *stream) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "attention_dropout_mask: the dropout rate must lie in [0, 1)");
+    if (int rc = need_init()) return rc;
+    if (!is_float_type(dtype)) return fail(PYGIM_ERR_INVALID, "attention_dropout_mask: type must be FLT32 or DBL64");
+    if (nnz < 0 || nnz > 0x7FFFFFFFll || heads < 1 || heads > 0x7FFFFFFFll) return fail(PYGIM_ERR_INVALID, "bad attention_dropout_mask sizes");
+    if (nnz == 0) return 0;
+    if (!mask || !is_device_ptr(mask) || (entry_ids && !is_device_ptr(entry_ids)))
+        return fail(PYGIM_ERR_INVALID, "pygim_attention_dropout_mask needs device pointers");
+    const uint64_t total = (uint64_t)nnz * (uint64_t)heads;
+    with_elem_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_attn_dropout_mask<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, (uint32_t)heads, entry_ids,
+                           attn_dropout_args<T>(p, seed), (T *)mask);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pygim_attention_dropout_host(int64_t nnz, int64_t heads, int64_t e0, double p, uint64_t seed, uint8_t *keep) {
+    if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "attention_dropout_host: the dropout rate must lie in [0, 1)");
+    if (nnz < 0 || heads < 1 || heads > 0x7FFFFFFFll || e0 < 0 || e0 + nnz > 0x100000000ll || (nnz > 0 && !keep))
+        return fail(PYGIM_ERR_INVALID, "bad attention_dropout_host sizes");
+    const uint32_t thr = attn_dropout_threshold(p);
+    for (int64_t i = 0; i < nnz; i++)
+        for (int64_t k = 0; k < heads; k++)
+            keep[i * heads + k] = attn_dropout_keep((uint32_t)(e0 + i), (uint32_t)k, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), thr) ? 1 : 0;
     return 0;
 }
 

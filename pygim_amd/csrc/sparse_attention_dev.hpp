@@ -37,11 +37,13 @@ constexpr uint32_t SA_MAX_HEAD = 256;   // features of one head: 64 lanes x 4 sc
 // S is the storage type of Q, K, V and out, T the type of the products, the scores, lse, (m, l, acc) and the slots (S = T, or a 16-bit
 // S with T = float).  LH: lanes per head, L: lanes per entry (a multiple of LH, 64 / L entries side by side); both powers of two.
 // head0: the first head of this launch (blockIdx.y counts chunks of L / LH heads from there).
-template <typename T, typename S, int VEC, int NP>
+// DROP: attention dropout as in k_gat_gather -- pr into l unchanged, pr * w into the accumulate, w from (entry index base + kk, the lane's
+// head: head0 and the blockIdx.y chunk included, so the mask does not depend on the launch shape).
+template <typename T, typename S, int VEC, int NP, bool DROP = false>
 __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                    const S *__restrict__ Q, uint64_t ldq, const S *__restrict__ K, uint64_t ldk, const S *__restrict__ Vm,
                                                    uint64_t ldv, uint32_t h, uint32_t heads, uint32_t head0, T scale, uint32_t LH, uint32_t L, S *__restrict__ out,
-                                                   uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat) {
+                                                   uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr) {
     using V = typename SdVec<S, VEC>::type;
     constexpr int U = RG_U / NP;
     const uint32_t R = 64 / L;
@@ -182,8 +184,10 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
 #pragma unroll
                 for (int u = 0; u < U; u++)
                     if (ok[u]) {
-                        const T pr = es_exp(s[u] - M);
+                        T pr = es_exp(s[u] - M);
                         l = l + pr;
+                        if constexpr (DROP)
+                            pr = attn_dropout_keep(base + k0 + (uint32_t)u * R + grp, head, dr.seed_lo, dr.seed_hi, dr.thr) ? pr * dr.keep_w : T(0);
 #pragma unroll
                         for (int p = 0; p < NP; p++)
 #pragma unroll
@@ -220,15 +224,15 @@ inline LaunchShape head_gather_shape(uint32_t h, uint32_t heads, uint32_t V, boo
     return g;
 }
 
-template <typename T, typename S, int VEC>
+template <typename T, typename S, int VEC, bool DROP>
 inline void launch_sa_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Q, uint64_t ldq, const S *K, uint64_t ldk,
                                const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat,
-                               const LaunchShape &g, hipStream_t st) {
+                               const LaunchShape &g, const AttnDrop<T> &dr, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
 #define PYGIM_SA_LAUNCH(NP)                                                                                                                                    \
     for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                                  \
-    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, rowptr,  \
-                       colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * g.per, scale, g.LH, g.L, out, ldo, lse, ws, ws_stat)
+    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP, DROP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, rowptr,  \
+                       colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * g.per, scale, g.LH, g.L, out, ldo, lse, ws, ws_stat, dr)
     constexpr uint32_t MAX_NP = (SA_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);   // only the piece counts a head of SA_MAX_HEAD can need
     if (g.npl == 1) PYGIM_SA_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
@@ -240,10 +244,10 @@ inline void launch_sa_gather_v(const uint32_t *rowptr, const uint32_t *colind, u
 
 // 16-byte pieces (of the storage type) when a head's features fill whole pieces and every row of Q, K, V and out starts 16-byte aligned;
 // else one element per lane.  The caller has checked h / heads <= SA_MAX_HEAD.
-template <typename T, typename S = T>
+template <typename T, typename S = T, bool DROP = false>
 inline void launch_sparse_attention(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Q, uint64_t ldq, const S *K,
                                     uint64_t ldk, const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse,
-                                    void *workspace, hipStream_t st) {
+                                    void *workspace, hipStream_t st, const AttnDrop<T> &dr = AttnDrop<T>()) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
@@ -252,8 +256,8 @@ inline void launch_sparse_attention(const uint32_t *rowptr, const uint32_t *coli
     const bool aligned = ldq % V == 0 && ldk % V == 0 && ldv % V == 0 && ldo % V == 0 && (uintptr_t)Q % 16 == 0 && (uintptr_t)K % 16 == 0 &&
                          (uintptr_t)Vm % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
     const LaunchShape g = head_gather_shape(h, heads, V, aligned);
-    if (g.vec > 1) launch_sa_gather_v<T, S, (int)V>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, st);
-    else launch_sa_gather_v<T, S, 1>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, st);
+    if (g.vec > 1) launch_sa_gather_v<T, S, (int)V, DROP>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, st);
+    else launch_sa_gather_v<T, S, 1, DROP>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

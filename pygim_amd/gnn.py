@@ -83,11 +83,13 @@ class GATConv(torch.nn.Module):
     """PyG's GATConv arithmetic on the adjacency as given (no self loops are inserted, like the other layers here):
     x' = lin(x) as [N, H, F];  score of stored entry (i, j) = leaky_relu(a_dst[i] + a_src[j]) with a = (x' * att).sum(-1);
     p = softmax of the scores over the entries of row i;  out[i] = sum_j p[(i, j)] * x'[j] per head; heads concatenated or averaged.
-    ``fused=True``: everything after the two reductions ``a`` is one ``gat_aggregate`` call."""
+    ``fused=True``: everything after the two reductions ``a`` is one ``gat_aggregate`` call.
+    ``dropout``: PyG's attention dropout on ``p`` (a fresh mask per forward while training, none in ``eval()``), inside the fused kernel
+    or on the ``edge_softmax`` result."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused=False, **_):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused=False, dropout=0.0, **_):
         super().__init__()
-        self.fused = bool(fused)
+        self.fused, self.dropout = bool(fused), _att_dropout("GATConv", dropout)
         self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
         self.lin = Linear(in_channels, self.heads * self.out_channels, bias=False)
         self.att_src = torch.nn.Parameter(torch.empty(1, self.heads, self.out_channels))
@@ -98,21 +100,24 @@ class GATConv(torch.nn.Module):
         torch.nn.init.xavier_uniform_(self.att_dst)
 
     def forward(self, x, adj_t):
-        from .attention import EdgeGraph, edge_softmax, gat_aggregate, spmm_values
+        from .attention import EdgeGraph, _dropout_seed, dropout_mask, edge_softmax, gat_aggregate, spmm_values
 
         g = EdgeGraph.of(adj_t)
         H, F_ = self.heads, self.out_channels
+        drop = self.dropout if self.training else 0.0
         xp = self.lin(x).view(-1, H, F_)
         a_src = (xp * self.att_src).sum(-1)
         a_dst = (xp * self.att_dst).sum(-1)
         if self.fused:
-            out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope)
+            out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope, dropout=drop)
         else:
             row, col = g.row.long().to(x.device), g.col.long().to(x.device)
             score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
             if score.dtype in (torch.float16, torch.bfloat16):   # edge_softmax is float32 / float64: 16-bit scores go up, and
                 score = score.float()                             # spmm_values takes the float32 probabilities beside 16-bit features
             p = edge_softmax(g, score)
+            if drop > 0.0:
+                p = p * dropout_mask(g, H, drop, _dropout_seed(None), p.dtype).to(p.device)
             out = spmm_values(g, p, xp.reshape(-1, H * F_), heads=H)
         if not self.concat:
             out = out.view(-1, H, F_).mean(1)
@@ -123,11 +128,13 @@ class TransformerConv(torch.nn.Module):
     """PyG's TransformerConv arithmetic without edge features or ``beta``, on the adjacency as given: q = lin_query(x), k = lin_key(x),
     v = lin_value(x) as [N, H, F];  score of stored entry (i, j) = q[i] . k[j] / sqrt(F) per head;  p = softmax of the scores over the
     entries of row i;  out[i] = sum_j p[(i, j)] * v[j] per head; heads concatenated or averaged;  + lin_skip(x) with ``root_weight``.
-    ``fused=True``: scores, softmax and product are one ``sparse_attention`` kernel (heads wider than 256 features run unfused)."""
+    ``fused=True``: scores, softmax and product are one ``sparse_attention`` kernel (heads wider than 256 features run unfused).
+    ``dropout``: PyG's attention dropout on ``p``, active while training."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, root_weight=True, bias=True, fused=TRANSFORMER_FUSED_DEFAULT, **_):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, root_weight=True, bias=True, fused=TRANSFORMER_FUSED_DEFAULT, dropout=0.0,
+                 **_):
         super().__init__()
-        self.fused = bool(fused)
+        self.fused, self.dropout = bool(fused), _att_dropout("TransformerConv", dropout)
         self.heads, self.out_channels, self.concat, self.root_weight = int(heads), int(out_channels), bool(concat), bool(root_weight)
         width = self.heads * self.out_channels
         self.lin_key = Linear(in_channels, width, bias=bias)
@@ -139,7 +146,8 @@ class TransformerConv(torch.nn.Module):
         from .attention import EdgeGraph, sparse_attention
 
         g = EdgeGraph.of(adj_t)
-        out = sparse_attention(g, self.lin_query(x), self.lin_key(x), self.lin_value(x), heads=self.heads, fused=self.fused)
+        out = sparse_attention(g, self.lin_query(x), self.lin_key(x), self.lin_value(x), heads=self.heads, fused=self.fused,
+                               dropout=self.dropout if self.training else 0.0)
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(1)
         return out if self.lin_skip is None else out + self.lin_skip(x)
@@ -151,11 +159,13 @@ class GATv2Conv(torch.nn.Module):
     (i, j) = (att * leaky_relu(x_r[i] + x_l[j])).sum(-1) per head;  p = softmax of the scores over the entries of row i;
     out[i] = sum_j p[(i, j)] * x_l[j] per head; heads concatenated or averaged; + bias.
     ``fused=True`` (the default): everything after the two linear maps is ``gatv2_aggregate``'s fused forward and backward (heads wider
-    than 256 features run unfused); ``fused=False`` materialises ``[nnz, H * F]``."""
+    than 256 features run unfused); ``fused=False`` materialises ``[nnz, H * F]``.
+    ``dropout``: PyG's attention dropout on ``p``, active while training; fused, it lives in the forward and both backward gathers."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, fused=True, **_):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, fused=True,
+                 dropout=0.0, **_):
         super().__init__()
-        self.fused, self.share_weights = bool(fused), bool(share_weights)
+        self.fused, self.share_weights, self.dropout = bool(fused), bool(share_weights), _att_dropout("GATv2Conv", dropout)
         self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
         self.lin_l = Linear(in_channels, self.heads * self.out_channels, bias=bias)
         self.lin_r = self.lin_l if self.share_weights else Linear(in_channels, self.heads * self.out_channels, bias=bias)
@@ -173,10 +183,19 @@ class GATv2Conv(torch.nn.Module):
         x_l = self.lin_l(x)
         x_r = x_l if self.share_weights else self.lin_r(x)
         att = self.att if self.att.dtype == x_l.dtype else self.att.float()   # autocast: 16-bit features beside the float32 parameter
-        out = gatv2_aggregate(g, x_r, x_l, att, heads=self.heads, negative_slope=self.negative_slope, fused=self.fused)
+        out = gatv2_aggregate(g, x_r, x_l, att, heads=self.heads, negative_slope=self.negative_slope, fused=self.fused,
+                              dropout=self.dropout if self.training else 0.0)
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(1)
         return out if self.bias is None else out + self.bias
+
+
+def _att_dropout(name, p):
+    """a layer's ``dropout=`` (attention dropout, as in PyG): a rate in [0, 1), active only while the layer is training"""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: dropout must lie in [0, 1), got {p}")
+    return p
 
 
 def folded_epilogue(conv_bias, bn):
@@ -230,21 +249,24 @@ class GIN(_Stack):
 
 
 class GAT(_Stack):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=False):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=False, att_dropout=0.0):
         assert hidden_channels % heads == 0, "GAT: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
-                         lambda h: GATConv(h, h // heads, heads=heads, concat=True, fused=fused))
+                         lambda h: GATConv(h, h // heads, heads=heads, concat=True, fused=fused, dropout=att_dropout))
 
 
 class GATv2(_Stack):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, share_weights=False, fused=True):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, share_weights=False, fused=True,
+                 att_dropout=0.0):
         assert hidden_channels % heads == 0, "GATv2: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
-                         lambda h: GATv2Conv(h, h // heads, heads=heads, concat=True, share_weights=share_weights, fused=fused))
+                         lambda h: GATv2Conv(h, h // heads, heads=heads, concat=True, share_weights=share_weights, fused=fused,
+                                             dropout=att_dropout))
 
 
 class GraphTransformer(_Stack):
-    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=TRANSFORMER_FUSED_DEFAULT):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=TRANSFORMER_FUSED_DEFAULT,
+                 att_dropout=0.0):
         assert hidden_channels % heads == 0, "GraphTransformer: heads must divide hidden_channels (the heads are concatenated)"
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
-                         lambda h: TransformerConv(h, h // heads, heads=heads, concat=True, fused=fused))
+                         lambda h: TransformerConv(h, h // heads, heads=heads, concat=True, fused=fused, dropout=att_dropout))

@@ -25,7 +25,10 @@ warm-up.  JSON lines:
     pygim_gatv2_backward calls on its own.  There is no composition to compare with on this graph (one [nnz, h] float32 tensor is
     nnz * h * 4 bytes = 117 GB); fused against fused=False runs on --small-shape (products-mini: 1 000 000 entries, one [nnz, h] float32
     tensor = 1.02 GB, so the handful the composition and its autograd graph hold fit beside everything else).
-    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot|v2] [--forward-only] [--dtypes f32,bf16,f16]
+  attention dropout (--section dropout, on its own: profiles/exp_dropout.txt), heads = 1 and 8, FLT32 and BF16 (--dtypes), two rounds:
+    forward, and forward + backward, of gat_aggregate, sparse_attention and gatv2_aggregate at p = 0 and p = 0.5, and -- with
+    --parent-lib PATH, the parent commit's libpygim_hip.so loaded beside this build -- the parent's p = 0 calls between them.
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot|v2|dropout] [--forward-only] [--dtypes f32,bf16,f16]
   --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
   (profiles/exp_gat_fused.txt); all = base + fused."""
 import argparse
@@ -412,12 +415,101 @@ def base_section(g, x, rowptr, col, n, nnz, h, iters, dev, line):
          same_product=agree, frozen_mul_ms=round(mul_code, 3), frozen_mul_form=note[:120], frozen_mul_sweep_ms=round(mul_sweep, 3))
 
 
+class OtherBuild:
+    """another build of the library (the parent commit's libpygim_hip.so) loaded beside this one: inside ``with other:`` every call of
+    pygim_amd._lib goes to it, so the two builds are timed alternately in one process on the same tensors.  Only the entry points the
+    dropout section calls get their argument types, copied from this build's."""
+    NAMES = ("pygim_init_ranks", "pygim_release", "pygim_last_error", "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_sddmm",
+             "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
+             "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace")
+
+    def __init__(self, path):
+        import ctypes
+
+        self.mine = _lib.lib()
+        self.handle = ctypes.CDLL(os.path.abspath(path))
+        for name in self.NAMES:
+            src, dst = getattr(self.mine, name), getattr(self.handle, name)
+            dst.argtypes, dst.restype = src.argtypes, src.restype
+        with self:
+            _lib.init_ranks(1)
+
+    def __enter__(self):
+        _lib._lib = self.handle
+
+    def __exit__(self, *exc):
+        _lib._lib = self.mine
+
+
+def dropout_section(g, n, nnz, h, iters, dev, line, names, parent):
+    """what attention dropout costs: forward, and forward + backward, of gat_aggregate, sparse_attention and gatv2_aggregate at p = 0 and
+    p = 0.5, heads = 1 and 8, and the p = 0 calls of the parent build (--parent-lib) in the same run, alternating, two rounds"""
+    g.transposed()
+    g.entry_ids_t()
+    slope = 0.2
+    a32, b32, g32 = (synth.features(n, h, torch.float32, seed=sd, device=dev, kind="uniform") for sd in (5, 6, 8))
+    nb = max(2, iters // 3)
+    for name in names:
+        dt = HALF_DTYPES[name]
+        A, B, G = (t.to(dt) for t in (a32, b32, g32))
+        for heads in (1, 8):
+            hd = h // heads
+            gen = torch.Generator(device=dev).manual_seed(4)
+            a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+            a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+            att = torch.randn(h, device=dev, generator=gen) * hd ** -0.5
+            calls = {
+                "gat_aggregate": (lambda p: attention._run_gat_aggregate(g, a_dst, a_src, B, heads, slope, False, p, 9),
+                                  lambda p, t: attention.gat_aggregate(g, *t, slope, dropout=p, seed=9), (a_dst, a_src, B)),
+                "sparse_attention": (lambda p: attention._run_sparse_attention(g, A, B, B, heads, hd ** -0.5, False, p, 9),
+                                     lambda p, t: attention.sparse_attention(g, *t, heads=heads, dropout=p, seed=9), (A, B, B)),
+                "gatv2_aggregate": (lambda p: attention._run_gatv2_aggregate(g, A, B, att, heads, slope, False, p, 9),
+                                    lambda p, t: attention.gatv2_aggregate(g, *t, heads=heads, negative_slope=slope, dropout=p, seed=9), (A, B, att)),
+            }
+            for fn_name, (fwd, full, operands) in calls.items():
+                leaves = [t.clone().requires_grad_() for t in operands]
+
+                def step(p):
+                    for t in leaves:
+                        t.grad = None
+                    full(p, leaves).backward(G)
+
+                # one discarded pass per build: without it the first timing after a shape's tensors are allocated came out 2 - 3 % slow
+                # (profiles/exp_dropout.txt, first run)
+                timed(lambda: fwd(0.0), iters)
+                if parent is not None:
+                    with parent:
+                        timed(lambda: fwd(0.0), iters)
+                for rnd in range(2):
+                    rec = dict(what=f"{fn_name} dropout", x_dtype=name, heads=heads, round=rnd)
+                    rec["fwd_p0_ms"] = round(timed(lambda: fwd(0.0), iters), 3)
+                    if parent is not None:
+                        with parent:
+                            rec["fwd_parent_ms"] = round(timed(lambda: fwd(0.0), iters), 3)
+                    rec["fwd_p05_ms"] = round(timed(lambda: fwd(0.5), iters), 3)
+                    rec["fwdbwd_p0_ms"] = round(timed(lambda: step(0.0), nb), 2)
+                    if parent is not None:
+                        with parent:
+                            rec["fwdbwd_parent_ms"] = round(timed(lambda: step(0.0), nb), 2)
+                    rec["fwdbwd_p05_ms"] = round(timed(lambda: step(0.5), nb), 2)
+                    rec["fwd_p05_over_p0"] = round(rec["fwd_p05_ms"] / rec["fwd_p0_ms"], 4)
+                    rec["fwdbwd_p05_over_p0"] = round(rec["fwdbwd_p05_ms"] / rec["fwdbwd_p0_ms"], 4)
+                    if parent is not None:
+                        rec["fwd_p0_over_parent"] = round(rec["fwd_p0_ms"] / rec["fwd_parent_ms"], 4)
+                        rec["fwdbwd_p0_over_parent"] = round(rec["fwdbwd_p0_ms"] / rec["fwdbwd_parent_ms"], 4)
+                    line(**rec)
+                del leaves
+                torch.cuda.empty_cache()
+        del A, B, G
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot", "v2"])
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot", "v2", "dropout"])
+    ap.add_argument("--parent-lib", default=None, help="--section dropout: the parent commit's libpygim_hip.so, timed alternately in the same run")
     ap.add_argument("--small-shape", default="products-mini", help="--section v2: the graph on which fused=False fits in memory")
     ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half / dot: the storage types of the features to measure")
     ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
@@ -448,6 +540,10 @@ def main():
         del x
         v2_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")], args.small_shape,
                    backward=not args.forward_only)
+    if args.section == "dropout":
+        del x
+        dropout_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")],
+                        OtherBuild(args.parent_lib) if args.parent_lib else None)
     torch.ops.pim_ops.dpu_release()
 
 
