@@ -455,14 +455,58 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
                                int64_t nnz, const void *values /* A's order, or NULL */, const void *G, int64_t ldg,
                                const int32_t *arg, int64_t h, void *dX, int64_t ldd, void *stream);
 
+/* ---- several statistics of a row's stored entries in one gather (PNA-style aggregation: mean, min, max, std side by side) ----
+ *   pygim_spmm_multi_reduce:  out[r, j * h + f] = statistic stats[j] over the stored entries e of row r of X[colind[e], f]   (unit
+ *     weights: there is no values operand).  One pass over the stored entries, whatever the list: a lane carries S1 = sum x and
+ *     S2 = sum x * x (when SUM, MEAN, VAR or STD is asked for) and the pairs (max, entry) and (min, entry) (when MAX or MIN is) beside
+ *     one gather of X.  With n = the row's number of stored entries (duplicates count separately):
+ *       SUM  = S1          MEAN = S1 / n          VAR = max(S2 / n - MEAN * MEAN, 0)          STD = sqrt(VAR + eps)
+ *       MAX, MIN = the winning element of X itself; arg_max / arg_min, when not NULL ([nrows, h] int32, contiguous), receive the index
+ *       in stored order of the entry that won
+ *     The contract of pygim_spmm_reduce: device pointers only (stats is a HOST array of 1..6 distinct PYGIM_STAT_* codes), a valid CSR
+ *     guaranteed by the caller, nnz = 0, empty rows and any h >= 1 allowed, row strides ldx >= h and ldo >= nstats * h (columns of out
+ *     beyond nstats * h are not touched), work is only enqueued on `stream`, scratch from the caller (pygim_spmm_multi_reduce_workspace
+ *     bytes: a function of its arguments alone, -1 for bad arguments; 16-byte aligned; per run of 512 entries two slots of h elements of
+ *     every component carried, nothing else of size nnz), no atomics, no two kernels write the same row, the same bits on every launch.
+ *     Empty rows store 0 for SUM, MEAN, VAR, MAX and MIN, sqrt(eps) for STD (the formula at S1 = S2 = 0) and -1 in arg_max / arg_min.
+ *     Types: FLT32 and DBL64 compute in themselves.  FLT16 / BF16 ("16-bit features" above): X and out are stored in 16 bits, an element
+ *       of X is widened as it is folded (exact), S1, S2, the division, VAR and STD are float32, and every stored value is rounded once,
+ *       where its row is stored; MAX / MIN are elements of X, so their rounding is exact.
+ *     Bounds, with u = 1e-5 (float32 arithmetic) or 1e-12 (DBL64):
+ *       SUM, MEAN   the bits of pygim_spmm_reduce(PYGIM_REDUCE_MEAN, values = NULL) on the same operands (SUM: its numerator): the same
+ *                   order of additions and the same division, for the 16-bit types too
+ *       MAX, MIN, arg_max, arg_min   the bits of pygim_spmm_reduce MAX / MIN with values = NULL (16-bit X: of that call on X widened
+ *                   to FLT32): the lowest entry index wins a tie, a NaN never wins against a number, all NaN stores NaN and arg -1
+ *       VAR         within 3 u mean(x^2) of the two-pass value (S2 / n within u mean(x^2), MEAN^2 within 2 u mean(|x|)^2; the clamp only
+ *                   moves towards it)
+ *       STD         within bound(VAR) / STD + 2 epsilon STD, epsilon the machine epsilon of the arithmetic; STD >= sqrt(eps)
+ *       16-bit out  2^-8 |exact| (BF16) or 2^-11 |exact| (FLT16) more, for the one rounding
+ *       NaN and inf in X travel through S1 / S2 as IEEE addition carries them, into SUM, MEAN, VAR and STD of that (row, feature) alone.
+ *   PYGIM_ERR_INVALID: an integer type, an unknown or repeated statistic, nstats outside 1..6, arg_max / arg_min without MAX / MIN in
+ *     stats, STD with eps not finite or <= 0, ldo < nstats * h, h > 65535 * 128, a workspace that is too small or misaligned. */
+#define PYGIM_STAT_SUM 0
+#define PYGIM_STAT_MEAN 1
+#define PYGIM_STAT_MIN 2
+#define PYGIM_STAT_MAX 3
+#define PYGIM_STAT_VAR 4
+#define PYGIM_STAT_STD 5
+int64_t pygim_spmm_multi_reduce_workspace(int dtype, const int *stats, int nstats, int64_t nrows, int64_t nnz, int64_t h);
+int pygim_spmm_multi_reduce(int dtype, const int *stats /* host, 1..6 distinct */, int nstats, double eps, int64_t nrows,
+                            const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X, int64_t ldx, int64_t h,
+                            void *out /* [nrows, nstats * h] */, int64_t ldo, int32_t *arg_max, int32_t *arg_min /* [nrows, h] or NULL */,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- which kernel instantiation and lane layout a call of the entry points above gets ----
  * The decision their launchers take, from the host functions the launchers themselves call: no device is touched and nothing is
  * launched (like the *_workspace functions it works without a GPU and without pygim_init_*).  `kind` names the entry point, `dtype`
  * the storage type, `aligned` != 0 says that every row stride is a multiple of a 16-byte piece and every base pointer (the
- * workspace included) a multiple of 16 bytes.  heads is ignored by SDDMM, SPMM_REDUCE and SPMM_REDUCE_BACKWARD, h by EDGE_SOFTMAX
+ * workspace included) a multiple of 16 bytes.  heads is ignored by SDDMM, SPMM_REDUCE and SPMM_REDUCE_BACKWARD, h by EDGE_SOFTMAX;
+ * SPMM_MULTI_REDUCE (FLT32, DBL64, FLT16, BF16: the lane layout of the mean fold, whatever the statistics) has no heads and takes
+ * heads = 1 alone (anything else: PYGIM_ERR_INVALID)
  * (forward and backward are one kind: the backward only has one more pointer that must be aligned).
  *   out[0] vec       features per piece (per lane and load): 16 / element size, or 1
- *   out[1] pieces    pieces a lane holds at once: 1 or 2 (row walkers: SPMM_VALUES, SPMM_REDUCE, GAT_AGGREGATE, SPMM_REDUCE_BACKWARD),
+ *   out[1] pieces    pieces a lane holds at once: 1 or 2 (row walkers: SPMM_VALUES, SPMM_REDUCE, GAT_AGGREGATE, SPMM_REDUCE_BACKWARD,
+ *                    SPMM_MULTI_REDUCE),
  *                    1, 2 or 4 (head-wise: SPARSE_ATTENTION, GATV2_*), 1 .. 4 (SDDMM), 1 (EDGE_SOFTMAX)
  *   out[2] LH        lanes across the features of one head (head-wise kernels); L for the others
  *   out[3] L         lanes per entry (a power of two; 64 / L entries side by side in a wave)
@@ -478,7 +522,7 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
  *                                            heads, `heads` for EDGE_SOFTMAX) does not fill whole pieces / `aligned` is 0
  * Returns PYGIM_ERR_INVALID for what the entry point itself rejects for these numbers: an unknown kind, a type it does not take,
  * heads not dividing h, h / heads > 256 (head-wise), and h > 65535 * 128 for the row walkers -- one launch holds 65535 chunks, so
- * pygim_spmm_values, pygim_spmm_reduce, pygim_gat_aggregate, their *_workspace functions (-1) and pygim_spmm_reduce_backward
+ * pygim_spmm_values, pygim_spmm_reduce, pygim_spmm_multi_reduce, pygim_gat_aggregate, their *_workspace functions (-1) and pygim_spmm_reduce_backward
  * reject a wider row before any launch, whatever the alignment.                                                               */
 #define PYGIM_SHAPE_SPMM_VALUES 0
 #define PYGIM_SHAPE_SPMM_REDUCE 1
@@ -489,6 +533,7 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
 #define PYGIM_SHAPE_SDDMM 6
 #define PYGIM_SHAPE_EDGE_SOFTMAX 7
 #define PYGIM_SHAPE_SPMM_REDUCE_BACKWARD 8
+#define PYGIM_SHAPE_SPMM_MULTI_REDUCE 9
 #define PYGIM_SHAPE_PART_PIECE 1
 #define PYGIM_SHAPE_PART_CHUNK 2
 #define PYGIM_SHAPE_PART_HEADS 4

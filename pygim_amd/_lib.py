@@ -25,6 +25,7 @@ EXPORTS = [
     "pygim_gat_aggregate", "pygim_gat_aggregate_workspace", "pygim_sparse_attention", "pygim_sparse_attention_workspace",
     "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward", "pygim_gather_launch_shape",
+    "pygim_spmm_multi_reduce", "pygim_spmm_multi_reduce_workspace",
     "pygim_gat_aggregate_dropout", "pygim_sparse_attention_dropout", "pygim_gatv2_aggregate_dropout", "pygim_gatv2_backward_dropout",
     "pygim_attention_dropout_mask", "pygim_attention_dropout_host",
 ]
@@ -34,12 +35,13 @@ INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
 FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention, gatv2_* and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
+STAT_SUM, STAT_MEAN, STAT_MIN, STAT_MAX, STAT_VAR, STAT_STD = range(6)   # pygim_spmm_multi_reduce
 # pygim_gather_launch_shape: the kinds, the names of out[0..7] and the bits of "flags"
 (SHAPE_SPMM_VALUES, SHAPE_SPMM_REDUCE, SHAPE_GAT_AGGREGATE, SHAPE_SPARSE_ATTENTION, SHAPE_GATV2_AGGREGATE, SHAPE_GATV2_BACKWARD, SHAPE_SDDMM,
- SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD) = range(9)
+ SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD, SHAPE_SPMM_MULTI_REDUCE) = range(10)
 SHAPE_FIELDS = ("vec", "pieces", "LH", "L", "per", "chunks", "launches", "flags")
 SHAPE_PART_PIECE, SHAPE_PART_CHUNK, SHAPE_PART_HEADS, SHAPE_SCALAR_SIZE, SHAPE_SCALAR_ALIGN = 1, 2, 4, 8, 16
-GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, gat_aggregate and spmm_reduce_backward
+GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, spmm_multi_reduce, gat_aggregate and spmm_reduce_backward
 
 
 class PygimError(RuntimeError):
@@ -109,6 +111,10 @@ def lib():
         L.pygim_spmm_reduce_workspace.restype = c_i64
         L.pygim_spmm_reduce_backward.argtypes = [c_int, c_i64, vp, vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp]
         L.pygim_gather_launch_shape.argtypes = [c_int, c_int, c_i64, c_i64, c_int, p_i64]
+        p_int = ctypes.POINTER(c_int)
+        L.pygim_spmm_multi_reduce_workspace.argtypes = [c_int, p_int, c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_multi_reduce_workspace.restype = c_i64
+        L.pygim_spmm_multi_reduce.argtypes = [c_int, p_int, c_int, ctypes.c_double, c_i64, vp, vp, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, vp, vp, c_i64, vp]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -406,6 +412,28 @@ def spmm_reduce_backward(dtype, ncols, rowptr_t_ptr, rows_t_ptr, perm_ptr, nnz, 
     """dX[c] = sum over the entries of row c of A^T of (arg[r] == e ? values[e] * G[r] : 0): the gradient of max / min (FLT32 / DBL64)"""
     check(lib().pygim_spmm_reduce_backward(int(dtype), int(ncols), _vp(rowptr_t_ptr), _vp(rows_t_ptr), _vp(perm_ptr), int(nnz), _vp(val_ptr),
                                            _vp(g_ptr), int(ldg), _vp(arg_ptr), int(h), _vp(dx_ptr), int(ldd), _vp(stream)))
+
+
+def _stat_array(stats):
+    stats = [int(s) for s in stats]
+    return (ctypes.c_int * max(len(stats), 1))(*stats), len(stats)
+
+
+def spmm_multi_reduce_workspace(dtype, stats, nrows, nnz, h):
+    """bytes of scratch spmm_multi_reduce needs for this type, list of statistics (STAT_*) and shape (a function of the numbers alone)"""
+    arr, k = _stat_array(stats)
+    n = int(lib().pygim_spmm_multi_reduce_workspace(int(dtype), arr, k, int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_multi_reduce_workspace arguments")
+    return n
+
+
+def spmm_multi_reduce(dtype, stats, eps, nrows, rowptr_ptr, col_ptr, nnz, x_ptr, ldx, h, out_ptr, ldo, arg_max_ptr, arg_min_ptr, ws_ptr, ws_bytes, stream=0):
+    """out[r, j * h + f] = statistic stats[j] (STAT_*: sum, mean, min, max, var, std = sqrt(var + eps)) over the entries e of row r of
+    X[col[e], f], all in one gather; arg_max_ptr / arg_min_ptr: int32 [nrows, h] for the winning entries, or 0 (FLT32, DBL64, FLT16, BF16)"""
+    arr, k = _stat_array(stats)
+    check(lib().pygim_spmm_multi_reduce(int(dtype), arr, k, float(eps), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr), int(ldx), int(h),
+                                        _vp(out_ptr), int(ldo), _vp(arg_max_ptr), _vp(arg_min_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
 
 
 def gather_launch_shape(kind, dtype, h, heads=1, aligned=True):

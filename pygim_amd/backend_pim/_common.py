@@ -205,6 +205,14 @@ class SparseGroupBase:
 
         return matmul_reduce(self, B, reduce)
 
+    def mul_multi_reduce(self, B: torch.Tensor, reduces=("mean", "min", "max", "std"), eps: float = 1e-5):
+        """several statistics of every row's neighbourhood (``"sum"``, ``"mean"``, ``"min"``, ``"max"``, ``"var"``, ``"std"``) of B on
+        the raw tensor's structure with unit weights, concatenated as ``[rows, len(reduces) * h]`` from one gather
+        (``pygim_amd.reduce.spmm_multi_reduce``).  No group is created or used.  Differentiable in B (float32 / float64 / bfloat16 / float16)."""
+        from ..reduce import matmul_multi_reduce
+
+        return matmul_multi_reduce(self, B, reduces, eps)
+
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):
         assert nparts > 0

@@ -22,6 +22,9 @@
 //   * the workspace slots hold the raw (m, l, acc): h accumulators per slot as in k_row_gather, and behind them 2 numbers per head and
 //     slot; the division by l happens only where a finished row is stored.
 // No atomics, every order is fixed by the CSR: the same bits on every launch.
+//
+// The walk -- batch loop, row search, ballot of row ends, flush, slot addressing, fix-up -- exists three times: in k_row_gather
+// (row_gather_dev.hpp), here, and in k_multi_gather (spmm_multi_dev.hpp): a change to the walk has to be made there as well.
 #pragma once
 #include <hip/hip_runtime.h>
 

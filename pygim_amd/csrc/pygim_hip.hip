@@ -29,6 +29,7 @@
 #include "sparse_attention_dev.hpp"
 #include "gatv2_dev.hpp"
 #include "spmm_reduce_dev.hpp"
+#include "spmm_multi_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -597,7 +598,7 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
 
 }  // extern "C"
 
-// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward ----
+// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward, spmm_multi_reduce ----
 // f(T()) with T the element type of `dtype` (the caller has checked it); INTS = false: FLT32 / DBL64 only
 template <bool INTS = false, typename F> static void with_elem_type(int dtype, F &&f) {
     if constexpr (INTS) {
@@ -1047,6 +1048,66 @@ int pygim_spmm_reduce_backward(int dtype, int64_t ncols, const int32_t *rowptr_t
     return 0;
 }
 
+// the statistics list of pygim_spmm_multi_reduce: 1..6 distinct PYGIM_STAT_* codes; col[s] = the block of statistic s in a row of out, or -1
+static bool parse_multi_stats(const int *stats, int nstats, int64_t h, int32_t col[MS_COUNT], bool &moments, bool &best) {
+    static_assert(MS_SUM == PYGIM_STAT_SUM && MS_MEAN == PYGIM_STAT_MEAN && MS_MIN == PYGIM_STAT_MIN && MS_MAX == PYGIM_STAT_MAX &&
+                      MS_VAR == PYGIM_STAT_VAR && MS_STD == PYGIM_STAT_STD,
+                  "the codes of include/pygim_hip.h");
+    for (int s = 0; s < MS_COUNT; s++) col[s] = -1;
+    moments = best = false;
+    if (!stats || nstats < 1 || nstats > MS_COUNT) return false;
+    for (int j = 0; j < nstats; j++) {
+        const int s = stats[j];
+        if (s < 0 || s >= MS_COUNT || col[s] >= 0) return false;
+        col[s] = (int32_t)(j * h);
+        if (s == MS_MAX || s == MS_MIN) best = true;
+        else moments = true;
+    }
+    return true;
+}
+
+int64_t pygim_spmm_multi_reduce_workspace(int dtype, const int *stats, int nstats, int64_t nrows, int64_t nnz, int64_t h) {
+    int32_t col[MS_COUNT];
+    bool moments, best;
+    if (!is_gather_type(dtype) || nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
+    if (!parse_multi_stats(stats, nstats, h, col, moments, best)) return -1;
+    return (int64_t)multi_workspace_bytes(moments, best, (uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
+}
+
+int pygim_spmm_multi_reduce(int dtype, const int *stats, int nstats, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                            const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, int32_t *arg_max, int32_t *arg_min, void *workspace,
+                            int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_multi_reduce: type must be FLT32, DBL64, FLT16 or BF16");
+    int32_t col[MS_COUNT];
+    bool moments, best;
+    if (h < 1 || h > (int64_t)RG_MAX_H) return fail(PYGIM_ERR_INVALID, "bad spmm_multi_reduce sizes / strides");
+    if (!parse_multi_stats(stats, nstats, h, col, moments, best))
+        return fail(PYGIM_ERR_INVALID, "spmm_multi_reduce: stats must be 1 to 6 distinct PYGIM_STAT_* codes");
+    if ((arg_max && col[MS_MAX] < 0) || (arg_min && col[MS_MIN] < 0))
+        return fail(PYGIM_ERR_INVALID, "spmm_multi_reduce: arg_max / arg_min need PYGIM_STAT_MAX / _MIN in stats");
+    if (col[MS_STD] >= 0 && !(eps > 0.0 && eps <= 1.7976931348623157e308))
+        return fail(PYGIM_ERR_INVALID, "spmm_multi_reduce: PYGIM_STAT_STD needs a finite eps > 0");
+    if ((arg_max && (uintptr_t)arg_max % 4 != 0) || (arg_min && (uintptr_t)arg_min % 4 != 0))
+        return fail(PYGIM_ERR_INVALID, "spmm_multi_reduce: arg_max / arg_min must be 4-byte aligned");
+    if (ldo < (int64_t)nstats * h) return fail(PYGIM_ERR_INVALID, "bad spmm_multi_reduce sizes / strides");
+    if (int rc = check_csr_call("spmm_multi_reduce", "rowptr / colind / X / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {arg_max, nrows > 0, true}, {arg_min, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}},
+                                pygim_spmm_multi_reduce_workspace(dtype, stats, nstats, nrows, nnz, h), workspace, workspace_bytes))
+        return rc;
+    with_gather_types(dtype, [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        MultiStats<T> st;
+        for (int k = 0; k < MS_COUNT; k++) st.col[k] = col[k];
+        st.eps = col[MS_STD] >= 0 ? (T)eps : T(0);
+        launch_spmm_multi<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)X, (uint64_t)ldx, (uint32_t)h,
+                                (S *)out, (uint64_t)ldo, arg_max, arg_min, workspace, st, moments, best, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the launch shape of a gather entry point, from the functions its launcher calls; no device, no launch (like the *_workspace functions)
 int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int aligned, int64_t out[8]) {
     static_assert(LS_PART_PIECE == PYGIM_SHAPE_PART_PIECE && LS_PART_CHUNK == PYGIM_SHAPE_PART_CHUNK && LS_PART_HEADS == PYGIM_SHAPE_PART_HEADS &&
@@ -1055,13 +1116,14 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     if (!out) return PYGIM_ERR_INVALID;
     const bool head_wise = kind == PYGIM_SHAPE_SPARSE_ATTENTION || kind == PYGIM_SHAPE_GATV2_AGGREGATE || kind == PYGIM_SHAPE_GATV2_BACKWARD;
     const bool walker = kind == PYGIM_SHAPE_SPMM_VALUES || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_GAT_AGGREGATE ||
-                        kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD;
+                        kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD || kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE;
     bool type_ok;
     if (kind == PYGIM_SHAPE_SPMM_REDUCE) type_ok = dtype_size(dtype) != 0 || is_half_type(dtype);   // integers: max / min; 16-bit: the mean
     else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) type_ok = is_float_type(dtype);
     else type_ok = is_gather_type(dtype);
     if (!(head_wise || walker || kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_EDGE_SOFTMAX) || !type_ok) return PYGIM_ERR_INVALID;
     if (kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) heads = 1;   // they have none
+    if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE && heads != 1) return PYGIM_ERR_INVALID;   // it has none either, and says so: heads must be 1
     if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) h = heads;                                                                           // it has no h
     if (h < 1 || heads < 1 || heads > 0x7FFFFFFFll || h % heads != 0 || h > (walker ? (int64_t)RG_MAX_H : 0xFFFFFFFFll)) return PYGIM_ERR_INVALID;
     if (head_wise && h / heads > (int64_t)SA_MAX_HEAD) return PYGIM_ERR_INVALID;
@@ -1071,6 +1133,7 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     else if (kind == PYGIM_SHAPE_SDDMM) g = sddmm_shape((uint32_t)h, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) g = edge_softmax_shape((uint32_t)heads, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) g = spmm_reduce_bwd_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE) g = multi_gather_shape((uint32_t)h, V, aligned != 0);
     else g = row_gather_shape((uint32_t)h, (uint32_t)(h / heads), V, aligned != 0);
     const int64_t v[8] = {g.vec, g.npl, g.LH, g.L, g.per, g.chunks, g.launches, g.flags};
     for (int i = 0; i < 8; i++) out[i] = v[i];

@@ -23,6 +23,8 @@
 //
 // k_gat_gather / k_gat_fixup / k_gat_empty (gat_aggregate_dev.hpp) are a copy of this walker -- batch loop, row search, flush, slot
 // addressing, fix-up -- with an online softmax in place of the Fold: a change to the walk here has to be made there as well.
+// k_multi_gather / k_multi_fixup / k_multi_empty (spmm_multi_dev.hpp) are a second copy, with a tuple of partial results (two sums, two
+// (best, entry) pairs) in place of the Fold: a change to the walk here has to be made there as well.
 //
 // A Fold says what the walker cannot know:
 //   INDEXED   the partial result is a pair (value, index of the entry that holds it): aidx, the index slots and arg exist

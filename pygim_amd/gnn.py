@@ -25,6 +25,10 @@ dtypes as GATConv.
 GATv2Conv / GATv2 are PyG's GATv2Conv (Brody et al.) without self loops or edge features on ``pygim_amd.attention.gatv2_aggregate``: fused by
 default -- one forward kernel and two backward kernels per layer, nothing of size nnz -- because the composition holds ``[nnz, heads * out]``
 tensors; the same dtypes as GATConv.
+
+PNAConv / PNA are PyG's PNAConv with one tower, one linear pre-layer and no edge features on ``pygim_amd.reduce.spmm_multi_reduce``:
+mean, min, max and std (or any of sum / mean / min / max / var / std) of the neighbours' messages come from one gather per layer, no
+``[E, F]`` message tensor is formed; identity / amplification / attenuation scalers; float32 / float64, bfloat16 like ``SAGEConv(aggr="mean")``.
 """
 import torch
 import torch.nn.functional as F
@@ -34,6 +38,7 @@ from .quantize import message_and_aggregate
 
 
 TRANSFORMER_FUSED_DEFAULT = True   # the fused forward beat the composition in both rounds of profiles/exp_sparse_attention.txt
+PNA_FUSED_DEFAULT = True           # the fused call beat the composition 3.4 x (float32) / 4.0 x (bfloat16) forward in both rounds of profiles/exp_multi_reduce.txt
 
 
 class GCNConv(torch.nn.Module):
@@ -190,6 +195,78 @@ class GATv2Conv(torch.nn.Module):
         return out if self.bias is None else out + self.bias
 
 
+class PNAConv(torch.nn.Module):
+    """PyG's PNAConv (Corso et al.) with ``towers=1``, ``pre_layers=1`` and no edge features, on the adjacency as given:
+    message of stored entry (i, j) = pre_nn(cat[x_i, x_j]);  every aggregator over the entries of row i;  every scaler on the
+    concatenated aggregates;  out = lin(post_nn(cat[x, scaled aggregates])).
+
+    With one linear pre-layer the message is ``W . [x_i || x_j] + b = a_i + m_j`` with ``a = W_dst . x + b`` and ``m = W_src . x``
+    (W_dst, W_src: the two halves of pre_nn's weight), so no ``[E, F]`` tensor is formed -- with d the stored entries of row i:
+        mean_i = a_i + mean_j m_j      min_i = a_i + min_j m_j      max_i = a_i + max_j m_j
+        std_i  = std_j m_j             var_i = var_j m_j            sum_i = d_i a_i + sum_j m_j
+    and all the statistics of m are ONE ``spmm_multi_reduce`` (``fused=True``) or one ``spmm_reduce`` per statistic (``fused=False``).
+    Rows with d = 0 keep the kernel's empty-row values (0, and sqrt(eps) for std) without a_i, as PyG's scatter gives them.
+    std = sqrt(relu(var) + 1e-5), var = mean of squares minus squared mean.
+    Scalers (PyG's DegreeScalerAggregation, d clamped to 1): ``identity``; ``amplification``: ``log(d + 1) / avg_log``; ``attenuation``:
+    ``avg_log / log(d + 1)``.  ``avg_log`` = the mean of log(d + 1) over the nodes, from ``deg`` (a degree histogram, as PyG takes it) or,
+    without it, from the adjacency of the first forward (kept as a buffer).
+    float32 / float64, trainable; bfloat16 after ``.to(torch.bfloat16)`` or under ``torch.autocast``; one GPU."""
+
+    EPS = 1e-5
+
+    def __init__(self, in_channels, out_channels, aggregators=("mean", "min", "max", "std"), scalers=("identity", "amplification", "attenuation"),
+                 deg=None, post_layers=1, fused=None, towers=1, pre_layers=1, edge_dim=None, divide_input=False, **_):
+        super().__init__()
+        if towers != 1 or pre_layers != 1 or edge_dim is not None or divide_input:
+            raise NotImplementedError("PNAConv: only towers=1, pre_layers=1 and no edge features are implemented")
+        self.aggregators, self.scalers = tuple(aggregators), tuple(scalers)
+        if not self.aggregators or len(set(self.aggregators)) != len(self.aggregators) or any(
+                a not in ("sum", "mean", "min", "max", "var", "std") for a in self.aggregators):
+            raise ValueError(f"PNAConv: aggregators must be distinct names among sum, mean, min, max, var, std, got {aggregators!r}")
+        if not self.scalers or any(s not in ("identity", "amplification", "attenuation") for s in self.scalers):
+            raise ValueError(f"PNAConv: scalers must be among identity, amplification, attenuation, got {scalers!r}")
+        self.fused = PNA_FUSED_DEFAULT if fused is None else bool(fused)
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        F_ = self.in_channels
+        self.pre_nn = Linear(2 * F_, F_)
+        layers = [Linear((len(self.aggregators) * len(self.scalers) + 1) * F_, self.out_channels)]
+        for _i in range(int(post_layers) - 1):
+            layers += [ReLU(), Linear(self.out_channels, self.out_channels)]
+        self.post_nn = Sequential(*layers)
+        self.lin = Linear(self.out_channels, self.out_channels)
+        avg_log = float("nan")
+        if deg is not None:
+            deg = torch.as_tensor(deg).to(torch.float64)
+            avg_log = float((torch.log(torch.arange(deg.numel(), dtype=torch.float64) + 1) * deg).sum() / deg.sum())
+        self.register_buffer("avg_log", torch.tensor(avg_log, dtype=torch.float64))
+
+    def forward(self, x, adj_t):
+        if getattr(adj_t, "row_sharded", False):
+            raise NotImplementedError("PNAConv is not available on a RowShardAdj (one GPU only)")
+        from .attention import EdgeGraph
+        from .reduce import spmm_multi_reduce
+
+        g = EdgeGraph.of(adj_t)
+        F_ = self.in_channels
+        W, b = self.pre_nn.weight, self.pre_nn.bias
+        a = F.linear(x, W[:, :F_], b)   # the target's half of the message, with the bias
+        m = F.linear(x, W[:, F_:])      # the source's half: what is aggregated
+        agg = spmm_multi_reduce(g, m, self.aggregators, self.EPS, fused=self.fused)
+        d = (g.rowptr[1:] - g.rowptr[:-1]).to(x.device)
+        has = (d > 0).to(agg.dtype).unsqueeze(1)
+        own = {"mean": has, "min": has, "max": has, "sum": d.to(agg.dtype).unsqueeze(1)}
+        a = a.to(agg.dtype)
+        agg = torch.cat([agg[:, j * F_:(j + 1) * F_] + own[s] * a if s in own else agg[:, j * F_:(j + 1) * F_]
+                         for j, s in enumerate(self.aggregators)], 1)
+        logd = torch.log(d.clamp(min=1).to(torch.float64) + 1)
+        if torch.isnan(self.avg_log):   # no histogram was given: the first adjacency's own (rows without entries count as log(0 + 1) = 0, as in a histogram)
+            self.avg_log.copy_(torch.log(d.to(torch.float64) + 1).mean() if d.numel() else torch.tensor(1.0))
+        avg = self.avg_log.to(torch.float64)
+        scale = {"identity": None, "amplification": (logd / avg), "attenuation": (avg / logd)}
+        outs = [agg if scale[s] is None else agg * scale[s].to(agg.dtype).unsqueeze(1) for s in self.scalers]
+        return self.lin(self.post_nn(torch.cat([x, torch.cat(outs, 1)], 1)))
+
+
 def _att_dropout(name, p):
     """a layer's ``dropout=`` (attention dropout, as in PyG): a rate in [0, 1), active only while the layer is training"""
     p = float(p)
@@ -262,6 +339,13 @@ class GATv2(_Stack):
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
                          lambda h: GATv2Conv(h, h // heads, heads=heads, concat=True, share_weights=share_weights, fused=fused,
                                              dropout=att_dropout))
+
+
+class PNA(_Stack):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, aggregators=("mean", "min", "max", "std"),
+                 scalers=("identity", "amplification", "attenuation"), deg=None, post_layers=1, fused=None):
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: PNAConv(h, h, aggregators=aggregators, scalers=scalers, deg=deg, post_layers=post_layers, fused=fused))
 
 
 class GraphTransformer(_Stack):

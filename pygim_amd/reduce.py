@@ -1,4 +1,5 @@
-"""Aggregation with a reduction other than the sum: ``spmm_reduce`` (mean / max / min over the stored entries of every row).
+"""Aggregation with a reduction other than the sum: ``spmm_reduce`` (mean / max / min over the stored entries of every row) and
+``spmm_multi_reduce`` (several statistics of the same neighbourhood -- sum, mean, min, max, var, std -- from ONE gather).
 
 ``torch_sparse.matmul(adj, x, reduce=...)`` with ``"mean"``, ``"max"`` or ``"min"``: GraphSAGE's mean, max-pool SAGE, PNA- and GIN-style
 layers.  A reduction other than the sum cannot be compiled into a device group, so this is a functional entry point on the plain CSR
@@ -11,8 +12,15 @@ run).  Sums stay with ``mul`` / ``spmm_values``.
 * max / min: all six element types; among equal products the lowest entry index wins and ``return_arg`` hands out that index per
   (row, feature), -1 for empty rows; differentiable in X (float32 / float64): the gradient goes to the entry that won.
 
+* ``spmm_multi_reduce``: PyG's ``MultiAggregation`` / ``PNAConv`` list ``["mean", "min", "max", "std"]`` (any of ``sum``, ``mean``,
+  ``min``, ``max``, ``var``, ``std``) concatenated as ``[rows, k * h]``, unit weights (pygim_spmm_multi_reduce: the sums of x and of
+  x * x and the two (best, entry) pairs are held in registers beside one gather of X).  float32 / float64 / bfloat16 / float16
+  (float32 arithmetic, one rounding per stored value); sum / mean and max / min have the bits of the single-statistic calls;
+  var = max(mean(x^2) - mean(x)^2, 0), std = sqrt(var + eps); differentiable in X through kernels that exist (``spmm_values`` on the
+  transposed structure, pygim_spmm_reduce_backward); ``fused=False`` composes the same result from ``spmm_reduce`` calls.
+
 Not covered: the gradient of max / min with respect to ``value`` (it needs a masked SDDMM), double backward, integer mean,
-multi-head values, ``RowShardAdj`` / multi-GPU.
+multi-head values, edge weights or integer types in ``spmm_multi_reduce``, ``RowShardAdj`` / multi-GPU.
 """
 from __future__ import annotations
 
@@ -162,3 +170,175 @@ def matmul_reduce(adj, B: torch.Tensor, reduce: str):
     if value is not None:
         value = (value if reduce == "mean" else value.detach()).to(_compute_dtype(B.dtype) if reduce == "mean" else B.dtype)
     return spmm_reduce(EdgeGraph.of(adj), B, reduce, value=value)
+
+
+# ---- several statistics of a row's stored entries in one gather ----
+STAT_CODE = {"sum": 0, "mean": 1, "min": 2, "max": 3, "var": 4, "std": 5}   # PYGIM_STAT_*
+
+
+def _run_multi_reduce(g: EdgeGraph, X: torch.Tensor, stats, eps: float, want_max: bool, want_min: bool):
+    """X [ncols, h] contiguous on g.device, stats: PYGIM_STAT_* codes -> (out [nrows, k * h], arg_max, arg_min: int32 [nrows, h] or None)"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
+    h, k = X.size(1), len(stats)
+    out = torch.empty((g.nrows, k * h), dtype=X.dtype, device=g.device)
+    amax = torch.empty((g.nrows, h), dtype=torch.int32, device=g.device) if want_max else None
+    amin = torch.empty((g.nrows, h), dtype=torch.int32, device=g.device) if want_min else None
+    if g.nrows == 0:
+        return out, amax, amin
+    ws = _workspace(L.spmm_multi_reduce_workspace(dt, stats, g.nrows, g.nnz, h), g.device)
+    L.spmm_multi_reduce(dt, stats, eps, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), h, out.data_ptr(), k * h,
+                        0 if amax is None else amax.data_ptr(), 0 if amin is None else amin.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out, amax, amin
+
+
+def _unit_values_t(g: EdgeGraph, dtype):
+    """(graph of A^T, ones [nnz, 1]): unit-weight sums on the transposed structure through pygim_spmm_values; the ones are kept with the graph"""
+    gt, _ = g.transposed()
+    held = getattr(gt, "_ones", None)
+    if held is None:
+        held = gt._ones = {}
+    if dtype not in held:
+        held[dtype] = torch.ones((g.nnz, 1), dtype=dtype, device=g.device)
+    return gt, held[dtype]
+
+
+class SpmmMultiReduce(torch.autograd.Function):
+    """forward: one pygim_spmm_multi_reduce.  backward, with n = the counts clamped to 1 and G_s the gradient block of statistic s:
+        U  = (2 / n) [var > 0] (G_var + G_std / (2 std))          P = G_sum + G_mean / n - U * mean
+        dX = A^T P + X * (A^T U) + spmm_reduce_backward(arg_max, G_max) + spmm_reduce_backward(arg_min, G_min)
+    ([var > 0]: the subgradient of PyG's relu).  Saved: X, the mean and var-or-std blocks and the two arg tensors; nothing of size nnz."""
+
+    @staticmethod
+    def forward(ctx, g, X, names, eps, want_arg):
+        stats = [STAT_CODE[s] for s in names]
+        grad = ctx.needs_input_grad[1]
+        out, amax, amin = _run_multi_reduce(g, X, stats, eps, "max" in names and (want_arg or grad), "min" in names and (want_arg or grad))
+        ctx.g, ctx.names, ctx.eps = g, names, eps
+        h = X.size(1)
+        block = lambda s: out[:, names.index(s) * h:(names.index(s) + 1) * h] if s in names else None
+        spread = "std" if "std" in names else ("var" if "var" in names else None)
+        ctx.spread = spread
+        half = X.dtype in HALF_TYPES   # 16-bit blocks are rounded: the backward takes mean and var again in float32 instead
+        keep_spread = None if (spread is None or half) else block(spread)
+        keep_mean = None if (spread is None or half) else block("mean")
+        ctx.save_for_backward(X, keep_mean, keep_spread, amax, amin)
+        empty = lambda a: torch.empty(0, dtype=torch.int32, device=g.device) if a is None else a
+        amax_o, amin_o = empty(amax), empty(amin)
+        ctx.mark_non_differentiable(amax_o, amin_o)
+        return out, amax_o, amin_o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _a, _b):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        g, names, eps, spread = ctx.g, ctx.names, ctx.eps, ctx.spread
+        X, mean, sp, amax, amin = ctx.saved_tensors
+        ct = _compute_dtype(X.dtype)
+        h = X.size(1)
+        Gb = lambda s: G[:, names.index(s) * h:(names.index(s) + 1) * h].to(ct) if s in names else None
+        n = _counts(g, ct).unsqueeze(1)
+        U = P = None
+        if spread is not None:
+            if sp is None:   # 16-bit X: mean and var of the forward again, in float32
+                mv, _, _ = _run_multi_reduce(g, X.to(ct), [STAT_CODE["mean"], STAT_CODE["var"]], 0.0, False, False)
+                mean, var = mv[:, :h], mv[:, h:]
+                live, std = var > 0, torch.sqrt(var + eps)
+            else:
+                if mean is None:
+                    mean = _run_spmm_reduce(g, None, X, REDUCE_CODE["mean"], False)[0]
+                if spread == "std":   # var > 0 exactly where sqrt(var + eps) lies above sqrt(eps), up to the rounding of the sum
+                    std, live = sp, sp > torch.sqrt(torch.tensor(eps, dtype=ct, device=g.device))
+                else:
+                    std, live = None, sp > 0
+            t = Gb("var")
+            if "std" in names:
+                t = Gb("std") / (2 * std) if t is None else t + Gb("std") / (2 * std)
+            U = (2.0 / n) * live.to(ct) * t
+            P = -U * mean
+        for s, w in (("sum", None), ("mean", n)):
+            if s in names:
+                t = Gb(s) if w is None else Gb(s) / w
+                P = t if P is None else P + t
+        dX = None
+        if P is not None:
+            gt, ones = _unit_values_t(g, ct)
+            if U is None:
+                dX = _run_spmm_values(gt, ones, P.contiguous(), 1)
+            else:   # both products as one call on [P | U]
+                both = _run_spmm_values(gt, ones, torch.cat([P, U], 1), 1)
+                dX = both[:, :h] + X.to(ct) * both[:, h:]
+        for s, arg in (("max", amax), ("min", amin)):
+            if s in names:
+                L, code = _backend()
+                gt, perm32 = _transposed32(g)
+                Gs = Gb(s).contiguous()
+                d = torch.empty((g.ncols, h), dtype=ct, device=g.device)
+                if g.ncols > 0:
+                    L.spmm_reduce_backward(code[ct], g.ncols, gt.rowptr.data_ptr(), gt.col.data_ptr(), perm32.data_ptr(), g.nnz, 0, Gs.data_ptr(), h,
+                                           arg.data_ptr(), h, d.data_ptr(), h, _stream(g.device))
+                dX = d if dX is None else dX + d
+        return None, dX.to(X.dtype), None, None, None
+
+
+def _multi_reduce_composed(g: EdgeGraph, X: torch.Tensor, names, eps: float, want_arg: bool):
+    """the same statistics from one spmm_reduce call each (two for var / std): the comparison of the fused call, and differentiable
+    through the single calls' own gradients.  16-bit X is taken up to float32 and the result rounded once."""
+    ct = _compute_dtype(X.dtype)
+    Xc = X.to(ct)
+    n = _counts(g, ct).unsqueeze(1)
+    mean = spmm_reduce(g, Xc, "mean") if {"sum", "mean", "var", "std"} & set(names) else None
+    var = None
+    if {"var", "std"} & set(names):
+        var = torch.relu(spmm_reduce(g, Xc * Xc, "mean") - mean * mean)
+    blocks, args = [], {"max": None, "min": None}
+    for s in names:
+        if s in ("max", "min"):
+            v, args[s] = spmm_reduce(g, Xc, s, return_arg=True)
+            blocks.append(v)
+        else:
+            blocks.append({"sum": lambda: mean * n, "mean": lambda: mean, "var": lambda: var, "std": lambda: torch.sqrt(var + eps)}[s]())
+    out = torch.cat(blocks, 1).to(X.dtype)
+    return (out, args["max"], args["min"]) if want_arg else out
+
+
+def spmm_multi_reduce(graph, X: torch.Tensor, reduces=("mean", "min", "max", "std"), eps: float = 1e-5, return_arg: bool = False, fused: bool = True):
+    """``out[r, j * h + f] = reduces[j] over the stored entries e of row r of X[col[e], f]``: several statistics of one neighbourhood,
+    concatenated in the order of ``reduces``, from one pass over the stored entries (unit weights)
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; X [columns, h] in float32, float64, bfloat16 or float16 (16-bit:
+    float32 arithmetic, every stored value rounded once); reduces: distinct names among ``"sum"``, ``"mean"``, ``"min"``, ``"max"``,
+    ``"var"`` (``max(mean(x^2) - mean(x)^2, 0)``, PyG's VarAggregation) and ``"std"`` (``sqrt(var + eps)``, PNAConv's formula).  Empty
+    rows give 0, and ``sqrt(eps)`` for std.  ``return_arg``: returns ``(out, arg_max, arg_min)``, the int32 [rows, h] indices of the
+    entries that won (-1 for empty rows; the lowest index wins a tie), ``None`` for a statistic not asked for.  Differentiable in X;
+    no double backward.  ``fused=False`` composes the same result from one ``spmm_reduce`` call per statistic (two for var / std).
+    Runs on the device; CPU tensors are staged there and the results come back to X's device."""
+    names = tuple(reduces)
+    if not names or any(s not in STAT_CODE for s in names):
+        raise ValueError(f"spmm_multi_reduce: reduces must be names among {sorted(STAT_CODE)}, got {reduces!r}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"spmm_multi_reduce: a statistic is listed twice in {reduces!r}")
+    if X.dtype not in FLOAT_TYPES and X.dtype not in HALF_TYPES:
+        raise TypeError(f"spmm_multi_reduce: X must be float32, float64, bfloat16 or float16, got {X.dtype}")
+    g = EdgeGraph.of(graph)
+    if X.dim() != 2 or X.size(0) != g.ncols or X.size(1) < 1:
+        raise ValueError(f"spmm_multi_reduce: X must be [{g.ncols}, h], got {tuple(X.shape)}")
+    eps = float(eps)
+    if "std" in names and not (0.0 < eps < float("inf")):
+        raise ValueError(f"spmm_multi_reduce: std needs a finite eps > 0, got {eps}")
+    home = X.device
+    Xd = X.to(g.device).contiguous()
+    back = lambda a: None if a is None else a.to(home)
+    if not fused:
+        res = _multi_reduce_composed(g, Xd, names, eps, bool(return_arg))
+        return (res[0].to(home), back(res[1]), back(res[2])) if return_arg else res.to(home)
+    out, amax, amin = SpmmMultiReduce.apply(g, Xd, names, eps, bool(return_arg))
+    if not return_arg:
+        return out.to(home)
+    return out.to(home), (amax.to(home) if "max" in names else None), (amin.to(home) if "min" in names else None)
+
+
+def matmul_multi_reduce(adj, B: torch.Tensor, reduces=("mean", "min", "max", "std"), eps: float = 1e-5, fused: bool = True):
+    """``spmm_multi_reduce`` on the structure of a SparseTensor or a ``backend_pim`` wrapper (its stored values are not used: unit weights)"""
+    return spmm_multi_reduce(EdgeGraph.of(adj), B, reduces, eps, fused=fused)

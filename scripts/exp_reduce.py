@@ -5,7 +5,15 @@
   the torch composite for scale: index_reduce_ amax over the per-entry messages, in blocks of 2^23 entries (the messages of the whole
     graph would be 117 GB);
   the bytes pygim_spmm_reduce_workspace returns for this shape.
-    python scripts/exp_reduce.py [--iters 10]"""
+    python scripts/exp_reduce.py [--iters 10]
+--section multi: several statistics in one gather (pygim_spmm_multi_reduce) on the same graph, float32 and bfloat16, two rounds in one
+process, written to profiles/exp_multi_reduce.txt (--out) as JSON lines:
+  spmm_values with one head (the yardstick) and spmm_reduce mean in the same round;
+  spmm_multi_reduce for ("mean",), ("max", "min") with args, ("mean", "std"), ("mean", "min", "max", "std") with and without args;
+  the fused=False composition of the last (one spmm_reduce per statistic, two for std);
+  forward + backward of the four-statistic call, fused against composed, with the peak of allocated memory;
+  the bytes pygim_spmm_multi_reduce_workspace returns.
+    python scripts/exp_reduce.py --section multi [--iters 10] [--out profiles/exp_multi_reduce.txt]"""
 import argparse
 import json
 import os
@@ -30,12 +38,86 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def section_multi(args):
+    dev = torch.device("cuda", 0)
+    n, nnz, d_max = synth.SHAPES[args.shape]
+    h, iters = args.h, args.iters
+    rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    g = attention.EdgeGraph(rowptr, col, (n, n))
+    g.transposed()   # built once, outside the timings
+    out_path = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exp_multi_reduce.txt")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    sink = open(out_path, "w")
+
+    def line(**kw):
+        text = json.dumps({"graph": args.shape, "h": h, "nnz": nnz, **kw})
+        print(text, flush=True)
+        sink.write(text + "\n")
+        sink.flush()
+
+    S = red.STAT_CODE
+    four = ("mean", "min", "max", "std")
+    codes = lambda names: [S[s] for s in names]
+    ones = torch.ones(nnz, 1, device=dev)
+    for dtype, name, code in ((torch.float32, "float32", _lib.FLT32), (torch.bfloat16, "bfloat16", _lib.BF16)):
+        x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform").to(dtype)
+        gathered = nnz * h * x.element_size()
+        multi = lambda names, arg: red._run_multi_reduce(g, x, codes(names), 1e-5, arg and "max" in names, arg and "min" in names)
+        for rnd in range(2):
+            t = {"spmm_values_heads1": timed(lambda: attention._run_spmm_values(g, ones, x, 1), iters),
+                 "spmm_reduce_mean": timed(lambda: red._run_spmm_reduce(g, None, x, red.REDUCE_CODE["mean"], False), iters),
+                 "multi_mean": timed(lambda: multi(("mean",), False), iters),
+                 "multi_max_min_args": timed(lambda: multi(("max", "min"), True), iters),
+                 "multi_mean_std": timed(lambda: multi(("mean", "std"), False), iters),
+                 "multi_four": timed(lambda: multi(four, False), iters),
+                 "multi_four_args": timed(lambda: multi(four, True), iters)}
+            with torch.no_grad():
+                t["composed_four"] = timed(lambda: red.spmm_multi_reduce(g, x, four, fused=False), max(iters // 2, 1))
+            sv = t["spmm_values_heads1"]
+            line(what="forward", dtype=name, round=rnd, **{k + "_ms": round(v, 3) for k, v in t.items()},
+                 **{k + "_over_values": round(v / sv, 3) for k, v in t.items() if k != "spmm_values_heads1"},
+                 multi_four_gather_tb_s=round(gathered / t["multi_four"] / 1e9, 2), composed_over_fused=round(t["composed_four"] / t["multi_four"], 2))
+        G = synth.features(n, 4 * h, torch.float32, seed=1, device=dev, kind="uniform").to(dtype)
+
+        def step(fused):
+            xx = x.detach().requires_grad_()
+            red.spmm_multi_reduce(g, xx, four, fused=fused).backward(G)
+            return xx.grad
+
+        for rnd in range(2):
+            res = {}
+            for fused in (True, False):
+                step(fused)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                base = torch.cuda.memory_allocated(dev)
+                ms = timed(lambda: step(fused), max(iters // 2, 1))
+                res["fused" if fused else "composed"] = (ms, (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20)
+            line(what="forward + backward, four statistics", dtype=name, round=rnd, fused_ms=round(res["fused"][0], 3), composed_ms=round(res["composed"][0], 3),
+                 composed_over_fused=round(res["composed"][0] / res["fused"][0], 2), fused_peak_mib=round(res["fused"][1], 1),
+                 composed_peak_mib=round(res["composed"][1], 1))
+        d_f, d_c = step(True).float(), step(False).float()
+        line(what="gradient check", dtype=name, max_abs_fused_minus_composed=float((d_f - d_c).abs().max()), max_abs=float(d_c.abs().max()))
+        line(what="workspace bytes", dtype=name, **{"_".join(k): _lib.spmm_multi_reduce_workspace(code, codes(k), n, nnz, h)
+                                                    for k in (("mean",), ("max", "min"), ("mean", "std"), four)},
+             spmm_reduce_mean=_lib.spmm_reduce_workspace(code, red.REDUCE_CODE["mean"], n, nnz, h))
+        del x, G, d_f, d_c
+    sink.close()
+    torch.ops.pim_ops.dpu_release()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
+    ap.add_argument("--section", default="reduce", choices=("reduce", "multi"))
+    ap.add_argument("--out", default=None, help="--section multi: where the JSON lines go (default profiles/exp_multi_reduce.txt)")
     args = ap.parse_args()
+    if args.section == "multi":
+        return section_multi(args)
     dev = torch.device("cuda", 0)
     n, nnz, d_max = synth.SHAPES[args.shape]
     h, iters = args.h, args.iters
