@@ -23,8 +23,10 @@
 //     slot; the division by l happens only where a finished row is stored.
 // No atomics, every order is fixed by the CSR: the same bits on every launch.
 //
-// The walk -- batch loop, row search, ballot of row ends, flush, slot addressing, fix-up -- exists three times: in k_row_gather
-// (row_gather_dev.hpp), here, and in k_multi_gather (spmm_multi_dev.hpp): a change to the walk has to be made there as well.
+// The walk inside k_gat_gather -- batch loop, row search, ballot of row ends, cut into stretches, slot rule -- is a copy of
+// k_row_gather's (row_gather_dev.hpp, which lists all the copies and says why they stay: a shared device function cost some
+// instantiations a wave per SIMD): a change to the walk has to be made there as well.  The fix-up's preamble (rg_cut_row) and the
+// choice of launch form (rg_dispatch) are shared.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -223,13 +225,9 @@ __global__ __launch_bounds__(256) void k_gat_fixup(const uint32_t *__restrict__ 
                                                    T *__restrict__ lse) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint64_t e_begin = w * RG_EPW;
-    if (e_begin + RG_EPW >= nnz) return;   // the last run has no row that goes on
-    const uint32_t e_end = (uint32_t)(e_begin + RG_EPW);
-    const uint32_t row = sd_row_of(rowptr, 0, nrows, e_end - 1);
-    const uint32_t rb = rowptr[row], re = rowptr[row + 1];
-    if (re <= e_end || rb < (uint32_t)e_begin) return;
-    const uint64_t w1 = (re - 1) / RG_EPW;
+    uint32_t row, rb, re;
+    uint64_t w1;
+    if (!rg_cut_row(rowptr, nrows, nnz, w, row, rb, re, w1)) return;
     const uint32_t hd = h / heads;
     for (uint32_t f = lane; f < h; f += 64) {
         const uint32_t k = f / hd;
@@ -264,17 +262,10 @@ template <typename T, typename S, int VEC, bool DROP>
 inline void launch_gat_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, const LaunchShape &g,
                                 const AttnDrop<T> &dr, hipStream_t st) {
-    const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    if (g.L < 64) {
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, false, DROP>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, g.L,
-                           out, ldo, lse, ws, ws_stat, dr);
-    } else if (g.npl == 1) {
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 1, true, DROP>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, 64u,
-                           out, ldo, lse, ws, ws_stat, dr);
-    } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, 2, true, DROP>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst, a_src, heads,
-                           slope, X, ldx, h, 64u, out, ldo, lse, ws, ws_stat, dr);
-    }
+    rg_dispatch(nnz, g, [&](auto nv, auto whole, dim3 grid, uint32_t L) {
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, decltype(nv)::value, decltype(whole)::value, DROP>), grid, dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst,
+                           a_src, heads, slope, X, ldx, h, L, out, ldo, lse, ws, ws_stat, dr);
+    });
 }
 
 // 16-byte pieces (of the storage type) under the conditions of launch_row_gather: aligned rows of X and out, and no piece across two heads

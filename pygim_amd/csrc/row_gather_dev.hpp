@@ -21,10 +21,18 @@
 // No atomics; every fold has a fixed order (entry order inside a run, the xor tree, then the runs in order): the same bits on every
 // launch.
 //
-// k_gat_gather / k_gat_fixup / k_gat_empty (gat_aggregate_dev.hpp) are a copy of this walker -- batch loop, row search, flush, slot
-// addressing, fix-up -- with an online softmax in place of the Fold: a change to the walk here has to be made there as well.
-// k_multi_gather / k_multi_fixup / k_multi_empty (spmm_multi_dev.hpp) are a second copy, with a tuple of partial results (two sums, two
-// (best, entry) pairs) in place of the Fold: a change to the walk here has to be made there as well.
+// What the siblings share with this file, and what they do not:
+//   * rg_cut_row -- which row goes on after run w, and up to which run -- is the preamble of k_row_gather_fixup, k_gat_fixup
+//     (gat_aggregate_dev.hpp) and k_multi_fixup (spmm_multi_dev.hpp); rg_dispatch is the host's choice between the three launch forms
+//     of row_gather_shape for launch_row_gather_v, launch_gat_gather_v and launch_multi_gather_v.
+//   * The walk inside the gather kernel -- batch loop, row search, ballot of row ends, cut into stretches, slot rule -- is still copied
+//     text in k_gat_gather, k_multi_gather, k_sa_gather (sparse_attention_dev.hpp), k_gatv2_gather and k_gatv2_grad (gatv2_dev.hpp):
+//     a change to the walk here has to be made in those five as well.  One device function for it, taking the kernel's per-batch
+//     load, its fold of a stretch and its row close as three lambdas, was written and measured (profiles/walker_refactor_resources.txt):
+//     every call inlines and no form uses scratch, but a fold body that is optimised as a function of its own before it is inlined does
+//     not come out as the same body written in the kernel, and in every form tried some instantiations lose a wave per SIMD (27 of
+//     430 in the best one, k_row_gather and k_gat_gather among them).  Until a form keeps every instantiation's occupancy the
+//     copies stay.
 //
 // A Fold says what the walker cannot know:
 //   INDEXED   the partial result is a pair (value, index of the entry that holds it): aidx, the index slots and arg exist
@@ -279,6 +287,22 @@ __global__ __launch_bounds__(256) void k_row_gather(const uint32_t *__restrict__
     if (pending) flush(true, head_open ? 0u : 1u, 0u);   // the run's last row goes on in the next run
 }
 
+// The fix-up's half of the slot rule, shared by k_row_gather_fixup, k_gat_fixup and k_multi_fixup: does a row go on after run w?  Then
+// `row` is that row, [rb, re) its entries and w1 the last run it reaches: the row is slot 1 of run w joined with slot 0 of the runs
+// w + 1 .. w1, in that order.  A row that began before run w is the business of the run it began in.
+__device__ inline bool rg_cut_row(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t nnz, uint64_t w, uint32_t &row, uint32_t &rb, uint32_t &re,
+                                  uint64_t &w1) {
+    const uint64_t e_begin = w * RG_EPW;
+    if (e_begin + RG_EPW >= nnz) return false;   // the last run has no row that goes on
+    const uint32_t e_end = (uint32_t)(e_begin + RG_EPW);
+    row = sd_row_of(rowptr, 0, nrows, e_end - 1);
+    rb = rowptr[row];
+    re = rowptr[row + 1];
+    if (re <= e_end || rb < (uint32_t)e_begin) return false;
+    w1 = (re - 1) / RG_EPW;
+    return true;
+}
+
 // one wave per run: the row that goes on after run w = slot 1 of w joined with slot 0 of every later run the row reaches, in order
 template <typename T, typename S, typename Fold>
 __global__ __launch_bounds__(256) void k_row_gather_fixup(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t nnz, uint32_t h,
@@ -286,13 +310,9 @@ __global__ __launch_bounds__(256) void k_row_gather_fixup(const uint32_t *__rest
                                                           int32_t *__restrict__ arg) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint64_t e_begin = w * RG_EPW;
-    if (e_begin + RG_EPW >= nnz) return;   // the last run has no row that goes on
-    const uint32_t e_end = (uint32_t)(e_begin + RG_EPW);
-    const uint32_t row = sd_row_of(rowptr, 0, nrows, e_end - 1);
-    const uint32_t rb = rowptr[row], re = rowptr[row + 1];
-    if (re <= e_end || rb < (uint32_t)e_begin) return;
-    const uint64_t w1 = (re - 1) / RG_EPW;
+    uint32_t row, rb, re;
+    uint64_t w1;
+    if (!rg_cut_row(rowptr, nrows, nnz, w, row, rb, re, w1)) return;
     for (uint32_t f = lane; f < h; f += 64) {
         uint64_t at = (w * 2 + 1) * (uint64_t)h + f;
         T s = ws[at];
@@ -354,20 +374,22 @@ inline LaunchShape row_gather_shape(uint32_t h, uint32_t width, uint32_t V, bool
     return g;
 }
 
+// the three launch forms of a row_gather_shape, for k_row_gather, k_gat_gather and k_multi_gather alike:
+// launch(integral_constant<int, NV>, bool_constant<WHOLE>, grid, L) starts the kernel's <.., NV, WHOLE, ..> form on that grid
+template <typename Launch> inline void rg_dispatch(uint64_t nnz, const LaunchShape &g, Launch &&launch) {
+    const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
+    if (g.L < 64) launch(std::integral_constant<int, 1>(), std::false_type(), dim3(blocks), g.L);
+    else if (g.npl == 1) launch(std::integral_constant<int, 1>(), std::true_type(), dim3(blocks), 64u);
+    else launch(std::integral_constant<int, 2>(), std::true_type(), dim3(blocks, g.chunks), 64u);   // two pieces per lane, the rest of a wider row over blockIdx.y
+}
+
 template <typename T, typename S, int VEC, typename Fold>
 inline void launch_row_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *values, uint32_t heads, const S *X,
                                 uint64_t ldx, uint32_t h, S *out, uint64_t ldo, int32_t *arg, T *ws, int32_t *ws_idx, const LaunchShape &g, hipStream_t st) {
-    const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    if (g.L < 64) {
-        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, false, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, g.L, out,
-                           ldo, arg, ws, ws_idx);
-    } else if (g.npl == 1) {
-        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 1, true, Fold>), dim3(blocks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values, heads, X, ldx, h, 64u, out,
-                           ldo, arg, ws, ws_idx);
-    } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_row_gather<T, S, VEC, 2, true, Fold>), dim3(blocks, g.chunks), dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
-                           heads, X, ldx, h, 64u, out, ldo, arg, ws, ws_idx);
-    }
+    rg_dispatch(nnz, g, [&](auto nv, auto whole, dim3 grid, uint32_t L) {
+        hipLaunchKernelGGL((k_row_gather<T, S, VEC, decltype(nv)::value, decltype(whole)::value, Fold>), grid, dim3(256), 0, st, rowptr, colind, nrows, nnz, values,
+                           heads, X, ldx, h, L, out, ldo, arg, ws, ws_idx);
+    });
 }
 
 // 16-byte pieces when every row of X and out starts 16-byte aligned, h fills whole pieces and no piece lies across two heads (arg and

@@ -12,9 +12,10 @@
 // NaN and inf travel through S1 / S2 as IEEE addition carries them, into sum, mean, var and std of that (row, feature) alone; the clamp
 // of var keeps a NaN (v < 0 ? 0 : v).
 //
-// k_multi_gather / k_multi_fixup / k_multi_empty are a copy of the walk of k_row_gather (row_gather_dev.hpp) -- batch loop, row search,
-// ballot of row ends, flush, slot addressing, fix-up -- with a tuple of partial results in place of the Fold: a change to the walk there
-// has to be made here as well (and in gat_aggregate_dev.hpp, the first copy).
+// The walk inside k_multi_gather -- batch loop, row search, ballot of row ends, cut into stretches, slot rule -- is a copy of
+// k_row_gather's (row_gather_dev.hpp, which lists all the copies and says why they stay), with a tuple of partial results in place of the
+// Fold: a change to the walk there has to be made here as well.  k_multi_fixup finds its row with rg_cut_row and launch_multi_gather_v
+// picks the launch form with rg_dispatch, both shared with k_row_gather and k_gat_gather.
 //
 // The workspace holds, per run, two slots of h elements of every component the instantiation carries: S1, S2 (MOMENTS), then the max
 // and min values and their two int32 index arrays (BEST); every sub-array starts 16-byte aligned.  A row that lies wholly inside a
@@ -244,20 +245,16 @@ __global__ __launch_bounds__(256) void k_multi_gather(const uint32_t *__restrict
 }
 
 // one wave per run: the row that goes on after run w = slot 1 of w joined with slot 0 of every later run the row reaches, in order
-// (the walk of k_row_gather_fixup: a change there has to be made here as well)
+// (the loop of k_row_gather_fixup on a tuple)
 template <typename T, typename S, bool MOMENTS, bool BEST>
 __global__ __launch_bounds__(256) void k_multi_fixup(const uint32_t *__restrict__ rowptr, uint32_t nrows, uint32_t nnz, uint32_t h, MultiWs<T> ws,
                                                      S *__restrict__ out, uint64_t ldo, int32_t *__restrict__ arg_max, int32_t *__restrict__ arg_min,
                                                      MultiStats<T> st) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint64_t e_begin = w * RG_EPW;
-    if (e_begin + RG_EPW >= nnz) return;   // the last run has no row that goes on
-    const uint32_t e_end = (uint32_t)(e_begin + RG_EPW);
-    const uint32_t row = sd_row_of(rowptr, 0, nrows, e_end - 1);
-    const uint32_t rb = rowptr[row], re = rowptr[row + 1];
-    if (re <= e_end || rb < (uint32_t)e_begin) return;
-    const uint64_t w1 = (re - 1) / RG_EPW;
+    uint32_t row, rb, re;
+    uint64_t w1;
+    if (!rg_cut_row(rowptr, nrows, nnz, w, row, rb, re, w1)) return;
     for (uint32_t f = lane; f < h; f += 64) {
         uint64_t at = (w * 2 + 1) * (uint64_t)h + f;
         T s1 = T(0), s2 = T(0), vmax = T(0), vmin = T(0);
@@ -320,17 +317,10 @@ template <typename T, typename S, int VEC, bool MOMENTS, bool BEST>
 inline void launch_multi_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *X, uint64_t ldx, uint32_t h, S *out,
                                   uint64_t ldo, int32_t *arg_max, int32_t *arg_min, const MultiWs<T> &ws, const MultiStats<T> &st, const LaunchShape &g,
                                   hipStream_t stream) {
-    const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
-    if (g.L < 64) {
-        hipLaunchKernelGGL((k_multi_gather<T, S, VEC, 1, false, MOMENTS, BEST>), dim3(blocks), dim3(256), 0, stream, rowptr, colind, nrows, nnz, X, ldx, h, g.L,
-                           out, ldo, arg_max, arg_min, ws, st);
-    } else if (g.npl == 1) {
-        hipLaunchKernelGGL((k_multi_gather<T, S, VEC, 1, true, MOMENTS, BEST>), dim3(blocks), dim3(256), 0, stream, rowptr, colind, nrows, nnz, X, ldx, h, 64u,
-                           out, ldo, arg_max, arg_min, ws, st);
-    } else {   // two pieces per lane, the rest of a wider row over blockIdx.y
-        hipLaunchKernelGGL((k_multi_gather<T, S, VEC, 2, true, MOMENTS, BEST>), dim3(blocks, g.chunks), dim3(256), 0, stream, rowptr, colind, nrows, nnz, X,
-                           ldx, h, 64u, out, ldo, arg_max, arg_min, ws, st);
-    }
+    rg_dispatch(nnz, g, [&](auto nv, auto whole, dim3 grid, uint32_t L) {
+        hipLaunchKernelGGL((k_multi_gather<T, S, VEC, decltype(nv)::value, decltype(whole)::value, MOMENTS, BEST>), grid, dim3(256), 0, stream, rowptr, colind,
+                           nrows, nnz, X, ldx, h, L, out, ldo, arg_max, arg_min, ws, st);
+    });
 }
 
 template <typename T, typename S, bool MOMENTS, bool BEST>
