@@ -74,23 +74,23 @@ def lds_rows_per_tile(nrows, nslices, rmax=LDS_ROWS_MAX, cus=CUS):
     return min(rmax, max(16, -(-nrows // tiles2)))
 
 
-def lds_product_seconds(nrows, ncols, nnz, h, es):
-    """the LDS-staged product on one GPU, or None where the library keeps the sweep (4-byte elements, rows of at least 17
-    elements, enough stored entries per staged column); uniform columns assumed (every tile streams every chunk)"""
+def lds_form(nrows, ncols, nnz, h, es):
+    """which LDS-staged form the library gives one GPU's part, restated from lds_choose_form (pygim_amd/csrc/lds_form.hpp) for 4-byte
+    elements, unit weights, default tunables and CUS compute units; uniform columns assumed (every tile streams every chunk).
+    Returns (keeps the sweep, split, tall, tail_rows, half, tiles): column ranges per row tile, full-height row tiles, rows left to
+    the tail kernels, half-split or not, row tiles of the plan.  The sweep is kept for other element sizes, for products of fewer
+    than LDS_MIN_LANES lanes and below the reuse rule.  profiles/exp_lds_form.txt lists where this restatement and the library part."""
+    sweep = (True, 1, 0, 0, False, 0)
     if es != 4 or h < LDS_MIN_LANES or nrows == 0 or nnz == 0:
-        return None
+        return sweep
     nsl = -(-h // 64)
-    pack_s = ncols * h * es * 2 / RATE_STREAM
-    cols_x = ncols      # columns a row tile stages
-    ns_entry = LDS_NS_PER_ENTRY
-    if LDS_HALF_SPLIT and h * es <= 128 and ncols >= 4 * 128:
-        # (round 6) products of at most 32 lanes: two column ranges in the halves of a wave -- a staged row holds X[c] and X[c + H], every tile stages half the rows
-        # (and meets twice the entries per chunk): all rows x 32 features 0.59 -> 0.49 ms
-        cols_x = -(-ncols // 2)
-        ns_entry = LDS_NS_PER_ENTRY_HALF
-    # (narrow products gather fewer bytes per entry on the sweep: their plans must serve more entries per staged column; rt_plans.inc)
-    min_reuse = LDS_MIN_REUSE if h * es > 128 else max(LDS_MIN_REUSE, LDS_MIN_REUSE_NARROW * (1.6 if cols_x != ncols else 1.0))
-    # short row shares (pygim_hip.hip build_lds_plan): full-height tiles split into S column ranges, each workgroup lands 1 / S of X
+    # (round 6) products of at most 32 lanes: two column ranges in the halves of a wave -- a staged row holds X[c] and X[c + H], every tile stages half the rows
+    # (and meets twice the entries per chunk): all rows x 32 features 0.59 -> 0.49 ms
+    half = bool(LDS_HALF_SPLIT and h * es <= 128 and ncols >= 4 * 128)
+    cols_x = -(-ncols // 2) if half else ncols      # columns a row tile stages
+    # (narrow products gather fewer bytes per entry on the sweep: their plans must serve more entries per staged column; lds_form.hpp)
+    min_reuse = LDS_MIN_REUSE if h * es > 128 else max(LDS_MIN_REUSE, LDS_MIN_REUSE_NARROW * (1.6 if half else 1.0))
+    # short row shares: full-height tiles split into S column ranges, each workgroup lands 1 / S of X
     tall = -(-int(nrows) // LDS_ROWS_MAX)
     split = min(8, CUS // (tall * nsl)) if tall * nsl * 2 <= CUS else 1
     tail_rows = 0
@@ -109,20 +109,37 @@ def lds_product_seconds(nrows, ncols, nnz, h, es):
                 break
     if LDS_COL_SPLIT and nnz >= (1 << 20) and split > 1:
         if nnz / (tall * cols_x) < min_reuse:
-            return None
+            return sweep
         tall2 = CUS // (nsl * split)            # (round 6) more, lighter row tiles when tall x slices x ranges leaves compute units idle
-        if not tail_rows and tall < tall2 <= 2 * tall:
-            tall = tall2
-        per_wg = max(cols_x / split * LDS_NS_PER_COLUMN + nnz / tall / split * ns_entry, cols_x / split * LDS_NS_PER_COLUMN_FLOOR) * 1e-9
+        tiles = tall2 if not tail_rows and tall < tall2 <= 2 * tall else tall
+        return False, split, tall, tail_rows, half, tiles
+    tiles = -(-int(nrows) // lds_rows_per_tile(int(nrows), nsl))
+    if nnz / (tiles * cols_x) < min_reuse:
+        return sweep
+    return False, 1, tall, 0, half, tiles
+
+
+def lds_form_seconds(form, nrows, ncols, nnz, h, es):
+    """the price of a form of lds_form: the slowest workgroup of every round, the pack of X and, for column ranges, their reduction"""
+    sweep, split, _, tail_rows, half, tiles = form
+    if sweep:
+        return None
+    nsl = -(-h // 64)
+    pack_s = ncols * h * es * 2 / RATE_STREAM
+    cols_x = -(-ncols // 2) if half else ncols
+    ns_entry = LDS_NS_PER_ENTRY_HALF if half else LDS_NS_PER_ENTRY
+    if split > 1:
+        per_wg = max(cols_x / split * LDS_NS_PER_COLUMN + nnz / tiles / split * ns_entry, cols_x / split * LDS_NS_PER_COLUMN_FLOOR) * 1e-9
         reduce_s = (split + 1) * nrows * h * es / RATE_STREAM
         return per_wg + reduce_s + pack_s + 2 * LAUNCH + (TAIL_S if tail_rows else 0.0)
-    rpt = lds_rows_per_tile(int(nrows), nsl)
-    tiles = -(-int(nrows) // rpt)
-    if nnz / (tiles * cols_x) < min_reuse:
-        return None
     per_wg = max(cols_x * LDS_NS_PER_COLUMN + nnz / tiles * ns_entry, cols_x * LDS_NS_PER_COLUMN_FLOOR) * 1e-9
     rounds = -(-tiles * nsl // CUS)
     return rounds * per_wg + pack_s + LAUNCH
+
+
+def lds_product_seconds(nrows, ncols, nnz, h, es):
+    """the LDS-staged product on one GPU, or None where the library keeps the sweep (lds_form)"""
+    return lds_form_seconds(lds_form(nrows, ncols, nnz, h, es), nrows, ncols, nnz, h, es)
 
 
 def product_seconds(nrows, ncols, nnz, h, es):

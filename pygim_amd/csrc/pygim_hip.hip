@@ -21,6 +21,7 @@
 #include "lds_reorder_dev.hpp"
 #include "lds_hybrid_dev.hpp"
 #endif
+#include "lds_form.hpp"
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
 #include "row_gather_dev.hpp"

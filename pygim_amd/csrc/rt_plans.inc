@@ -284,18 +284,19 @@ int build_lds_plan(Part &p, size_t es, int *d_flag_sorted, hipStream_t st, const
     return rc;
 }
 
-// The ring of a code-stream plan: buffers and columns per chunk (from the tunables; whole 1 KiB pieces per wave, inside the LDS).
-static void code_ring(uint32_t NW, uint32_t row_bytes, uint32_t &NBUF, uint32_t &KC) {
-    int64_t nbuf = g_tune.lds_code_nbuf;
-    if (nbuf == 0) nbuf = NW == 8 ? LDS_CODE8_AUTO_NBUF : 2;
-    nbuf = std::min<int64_t>(std::max<int64_t>(nbuf, 2), 10);
-    static const uint32_t kc_of[11] = {0, 0, 320, 192, 160, 128, 96, 64, 64, 64, 64};
-    uint32_t kc = g_tune.lds_code_kc > 0 ? (uint32_t)g_tune.lds_code_kc : kc_of[nbuf] * 256 / row_bytes;
-    const uint32_t kq = 1024 * NW / row_bytes;                          // columns of one 1 KiB piece per wave
-    kc = std::max(kq, kc / kq * kq);                                    // whole pieces per wave
-    while ((uint64_t)kc * row_bytes * (uint64_t)nbuf > LDS_BYTES || kc * (uint32_t)nbuf > 640) kc -= kq;   // (the LDS; 10-bit LDS rows in a token)
-    KC = kc;
-    NBUF = (uint32_t)nbuf;
+// The tunables the form decision reads (lds_form.hpp lds_choose_form), copied in this one place.
+static_assert(LDS_EL_INT8 == PYGIM_INT8 && LDS_EL_INT16 == PYGIM_INT16 && LDS_EL_INT32 == PYGIM_INT32 && LDS_EL_INT64 == PYGIM_INT64 &&
+              LDS_EL_FLT32 == PYGIM_FLT32 && LDS_EL_DBL64 == PYGIM_DBL64, "lds_form.hpp restates the element type codes");
+static LdsFormKnobs lds_form_knobs() {
+    LdsFormKnobs k;
+#define PYGIM_KNOB(name) k.name = g_tune.name
+    PYGIM_KNOB(lds_mode); PYGIM_KNOB(lds_min_reuse_x100); PYGIM_KNOB(lds_min_width); PYGIM_KNOB(lds_min_width8); PYGIM_KNOB(lds_min_reuse_narrow_x100);
+    PYGIM_KNOB(lds_waves); PYGIM_KNOB(lds_long_slots); PYGIM_KNOB(lds_code);
+    PYGIM_KNOB(lds_col_split); PYGIM_KNOB(lds_col_split_f32); PYGIM_KNOB(lds_row_tail); PYGIM_KNOB(lds_half_split); PYGIM_KNOB(lds_split_order); PYGIM_KNOB(lds_fill_tiles);
+    PYGIM_KNOB(lds_code_nbuf); PYGIM_KNOB(lds_code_waves); PYGIM_KNOB(lds_code_kc); PYGIM_KNOB(lds_code_boundary); PYGIM_KNOB(lds_code_exp);
+    PYGIM_KNOB(lds_round_tiles); PYGIM_KNOB(lds_tile_order); PYGIM_KNOB(lds_codegen); PYGIM_KNOB(lds_fail);
+#undef PYGIM_KNOB
+    return k;
 }
 
 // The rows an LDS plan leaves out (p.lds_rows .. nrows): their segment table for k_lds_tail_seg / _fin
@@ -348,7 +349,7 @@ int build_hybrid(Part &p, int dtype, size_t es, int *d_flag_sorted, hipStream_t 
     uint32_t cell_rows = LDS_CODE_AUTO_WAVES * LDS_CODE8_KA, cell_cols = 128, ring_nbuf = 0;
     if (g_tune.lds_round_tiles && h_hint > 0)
         cell_rows = lds_rows_per_tile((uint32_t)p.nrows, cell_rows, (uint32_t)((h_hint * (int64_t)std::max<size_t>(es, 2) + 255) / 256), (uint32_t)std::max(g_ctx.cu_count, 1));
-    code_ring(LDS_CODE_AUTO_WAVES, 256, ring_nbuf, cell_cols);
+    lds_code_ring(LDS_CODE_AUTO_WAVES, 256, lds_form_knobs(), LDS_BYTES, ring_nbuf, cell_cols);
     std::string why = hybrid_split_on_device(p.rowptr, p.colind, (uint32_t)p.nrows, (uint64_t)p.nnz, p.sim_order, cell_rows, cell_cols, min_cell, st, hs);
     // worth it when the dense cells hold a good share of the entries (the rest is gathered as before, plus one more pass over C)
     if (why.empty() && (double)hs.nnz_d < 0.3 * (double)p.nnz) {
@@ -498,242 +499,131 @@ static std::string codegen_verify(const Part &p, const LdsGeometry &geo, uint32_
     return std::string();
 }
 
-static int build_lds_plan_form(Part &p, size_t es, int *d_flag_sorted, hipStream_t st, const std::vector<uint32_t> &h_rowptr, int64_t h_hint,
-                               bool allow_code) {   // (es by value: INT8 plans are made as INT16 plans)
-    // PYGIM_PLAN_TIMING=1: where the creation time of an LDS-staged plan goes (stderr; the reference prints its own prepare / load times)
-    static const bool plan_timing = getenv("PYGIM_PLAN_TIMING") != nullptr;
+// What a producer of an LDS-staged plan (the device code generator, the host encoder) hands over: device arrays and counts.
+struct LdsBuilt {
+    void *code = nullptr;                  // code stream in executable memory (nullptr: a token plan)
+    uint64_t code_bytes = 0, pairs = 0, shared = 0;
+    uint32_t gsize = 0, nsets = 0;
+    uint64_t *d_start = nullptr;
+    uint32_t *d_tok = nullptr, *d_rowmap = nullptr;
+    LdsTile *d_tiles = nullptr;
+    uint32_t ntiles = 0, wdelta = 0;
+    uint64_t slots = 0, tokens = 0;
+    bool device = false;                   // written by the device code generator
+    void release() {
+        if (code) (void)hsa_amd_memory_pool_free(code);
+        for (void *q : {(void *)d_start, (void *)d_tok, (void *)d_rowmap, (void *)d_tiles})
+            if (q) (void)hipFree(q);
+    }
+};
+
+// The one place that writes a built plan into its part, whichever producer made it.
+static int adopt_lds_plan(Part &p, const LdsForm &f, const LdsGeometry &geo, const LdsBuilt &b, const std::vector<uint32_t> &h_rowptr) {
+    if (b.code) {
+        p.lds_code = (char *)b.code;
+        p.lds_code_bytes = b.code_bytes;
+        p.lds_code_start = b.d_start;
+        p.lds_code_pairs = b.pairs;
+        p.lds_code_shared = b.shared;
+        p.lds_is_code = true;
+        p.lds_code_piece = geo.KC * geo.row_bytes / geo.NW;
+        p.lds_code_gsize = b.gsize;
+        p.lds_code_nsets = b.nsets;
+        if (b.device) p.lds_codegen_device = true;
+    } else {
+        p.lds_tok = b.d_tok;
+        p.lds_wdelta = b.wdelta;
+    }
+    p.lds_rowmap = b.d_rowmap;
+    p.lds_tiles = b.d_tiles;
+    p.lds_col_splits = geo.col_splits;
+    p.lds_rows = f.rows_lds < (uint32_t)p.nrows ? f.rows_lds : 0;
+    p.lds_half = f.half_H;
+    p.lds_kc = geo.KC;
+    p.lds_nbuf = geo.NBUF;
+    p.lds_row_bytes = geo.row_bytes;
+    p.lds_ka = geo.KA;
+    p.lds_ntiles = b.ntiles;
+    p.lds_nw = geo.NW;
+    p.lds_batch = geo.BATCH;
+    p.lds_slots = b.slots;
+    p.lds_tokens = b.tokens;   // (a code stream has no padding: its entries)
+    return build_tail_segments(p, h_rowptr);
+}
+
+// PYGIM_PLAN_TIMING=1: where the creation time of an LDS-staged plan goes (stderr; the reference prints its own prepare / load times)
+struct PlanLap {
+    const bool on = getenv("PYGIM_PLAN_TIMING") != nullptr;
     double t_mark = now_ms();
-    auto lap = [&](const char *what) {
-        if (!plan_timing) return;
+    void operator()(const char *what) {
+        if (!on) return;
         const double t = now_ms();
         fprintf(stderr, "[pygim plan] %-34s %8.1f ms\n", what, t - t_mark);
         t_mark = t;
-    };
-    const size_t val_es = es;   // bytes of a stored value (es itself becomes 2 for INT8 below)
-    const bool int8_code = es == 1 && t_plan_dtype == PYGIM_INT8 && allow_code && g_tune.lds_code && g_tune.lds_waves == 16 && g_tune.lds_code_waves != 16;
-    if (es == 1) {   // INT8: the 8-wave INT16 code stream on features widened to 16 bits (no token form, no 16-wave form)
-        if (!int8_code) return 0;
-        es = 2;
     }
-    // INT64 / DBL64, unit weights: the 8-wave code stream on rows of 512 bytes (a register pair per value; no token form)
-    // (round 5: valued DBL64 too -- the value through an SGPR pair)
-    // valued INT64: the 64-bit product from 32-bit pieces (v_mul_lo_u32 + v_mad_u64_u32; values of any size, the encoders pick the form)
-    const bool el8_code = es == 8 && (t_plan_dtype == PYGIM_INT64 || t_plan_dtype == PYGIM_DBL64) && allow_code && g_tune.lds_code &&
-                          g_tune.lds_waves == 16 && g_tune.lds_code_waves != 16;
-    if (es == 8 && !el8_code) return 0;
-    if (g_tune.lds_mode == 2 || (es != 4 && es != 2 && es != 8) || p.is_extra || p.nnz == 0 || p.nrows == 0 || p.ncols == 0) return 0;
-    if ((p.vals || es == 2) && g_tune.lds_waves != 16) return 0;  // the valued and the INT16 kernels exist for the 16-wave geometry
-    if (h_hint > 0 && (es == 8 ? h_hint : (h_hint * (int64_t)std::max<size_t>(es, 2)) / 4) < (es == 8 ? g_tune.lds_min_width8 : g_tune.lds_min_width)) return 0;   // no product of this group is wide enough (want_lds; INT8 rides the INT16 stream: lanes of two features): no plan, no code
-    if ((uint64_t)p.ncols * (es == 8 ? 512ull : 256ull) >= (1ull << 32) - (1ull << 20) || (uint64_t)p.nnz >= (1ull << 31)) return 0;
-    LdsGeometry geo;
-    geo.NW = g_tune.lds_waves == 16 ? 16 : 8;
-    geo.KA = lds_ka(geo.NW);
-    geo.KC = LDS_KC;
-    geo.BATCH = lds_batch(geo.NW);
-    geo.keep_tile_order = p.lds_contig_tiles ? 1u : 0u;
-    // FLT32 / INT32 with unit weights: the code-stream form (the schedule compiled into machine code); its plan is built in the
-    // geometry of its kernels and serves no token kernel
-    // (valued matrices: FLT32 -- the value is the literal of a v_mul_f32 in the stream -- and, round 5, INT32: v_mul_lo_u32 is VOP3 and takes no
-    // literal on gfx9, so the value rides as an inline constant when every value of the matrix lies in [-16, 64], else through an SGPR)
-    const bool want_code = allow_code && g_tune.lds_code && geo.NW == 16 &&
-                           ((es == 4 && t_plan_dtype == PYGIM_FLT32) || (es == 4 && t_plan_dtype == PYGIM_INT32) ||
-                            (es == 2 && t_plan_dtype == PYGIM_INT16) || int8_code || el8_code);
-    const int64_t slice_b = es == 8 ? 512 : 256;   // bytes of a row of a slice
-    const int64_t nsl_hint = h_hint > 0 ? (h_hint * (int64_t)es + slice_b - 1) / slice_b : 4;
-    if (want_code) {
-        // 8 waves x 228 accumulators (2 waves per SIMD): tiles of 1 824 rows -- Reddit h = 256 is two rounds of workgroups on 256 CUs
-        // instead of three, a third less of X staged -- or round 3's 16 waves x 96
-        const int64_t cw = g_tune.lds_code_waves;
-        const bool eight = cw == 8 || (cw != 16 && LDS_CODE_AUTO_WAVES == 8) || int8_code || el8_code;
-        if (eight) {
-            geo.NW = 8;
-            geo.KA = el8_code ? LDS_CODE8_KA64 : LDS_CODE8_KA;
-            geo.BATCH = 8;
-        }
-        if (el8_code) geo.row_bytes = 512;
+};
+
+// Round 5: the code stream GENERATED ON THE DEVICE (lds_codegen_dev.hpp) from the resident CSR -- the same bytes the host encoder
+// would write (lds_codegen = 2 checks that, word for word) without the graph ever visiting the host.  A failure on the way is returned
+// as text (the host encoder takes over); only a mismatch under lds_codegen = 2 is an error (rc).
+static std::string lds_plan_on_device(const Part &p, const LdsForm &f, size_t val_es, hipStream_t st, const std::vector<uint32_t> &h_rowptr, const uint32_t *ro,
+                                      PlanLap &lap, LdsBuilt &b, int &rc) {
+    const size_t es = f.es;
+    const uint32_t ncols_plan = f.half_H ? f.half_H : (uint32_t)p.ncols;
+    CgDeviceResult dr;
+    std::string exec_why;
+    auto alloc_exec = [&](size_t bytes) -> void * { return exec_alloc(bytes, &exec_why); };
+    auto free_exec = [&](void *q) { (void)hsa_amd_memory_pool_free(q); };
+    // (round 5: valued INT16 / INT8 -- the values sign-extended to the 4-byte slot the encoders read: v_pk_mul_lo_u16 takes the low half)
+    uint32_t *d_vals32 = nullptr;
+    if (p.vals && val_es < 4) {
+        if (hipMalloc((void **)&d_vals32, std::max<size_t>((size_t)p.nnz * 4, 256)) != hipSuccess) {
+            (void)hipGetLastError();
+            d_vals32 = nullptr;
+        } else if (val_es == 1) hipLaunchKernelGGL((k_widen_vals<int8_t>), dim3((unsigned)(((uint64_t)p.nnz + 255) / 256)), dim3(256), 0, st, (const int8_t *)p.vals, (uint64_t)p.nnz, d_vals32);
+        else hipLaunchKernelGGL((k_widen_vals<int16_t>), dim3((unsigned)(((uint64_t)p.nnz + 255) / 256)), dim3(256), 0, st, (const int16_t *)p.vals, (uint64_t)p.nnz, d_vals32);
     }
-    // tiles sized so that one product of the group's width runs as whole rounds of workgroups (lds_plan.hpp)
-    if (g_tune.lds_round_tiles && h_hint > 0)
-        geo.rows_per_tile = lds_rows_per_tile((uint32_t)p.nrows, geo.NW * geo.KA, (uint32_t)nsl_hint, (uint32_t)std::max(g_ctx.cu_count, 1));
-    // a row share too short to fill the chip with workgroups that each stream a whole slice of X (a rank's share on N GPUs: 24 tiles x
-    // 4 slices on 256 CUs): full-height row tiles, each split into S column ranges -- S x as many workgroups, each landing 1/S of X;
-    // partial sums per range, reduced in range order (launch_lds).  Integers stay exact; FLT32 only when asked (lds_col_split_f32)
-    // Round 6: FLT32 too by default, for parts of a million entries and more (a rank's share of a large graph: 0.93 -> 0.45 ms for a 1/8 row share of the
-    // Reddit-shaped graph) -- a row's sum is then the sum of its column ranges' sums, inside the path's 1e-5 of |A|.|x| but no longer the CPU loop's bits;
-    // lds_col_split_f32 = 0 keeps the stored-order form, and the group's note says which one it got
-    const bool f32_split_ok = g_tune.lds_col_split_f32 == 1 ? p.nnz >= (1 << 20) : g_tune.lds_col_split_f32 != 0;
-    uint32_t rows_lds = (uint32_t)p.nrows;   // rows the plan's tiles will cover (fewer: see below)
-    if (g_tune.lds_col_split != 1 && (geo.NW == 16 || want_code) && !el8_code && (t_plan_dtype != PYGIM_FLT32 || f32_split_ok) && !p.vals) {   // (round 6: INT8 too)
-        const uint32_t cus = (uint32_t)std::max(g_ctx.cu_count, 1);
-        const uint64_t nsl = h_hint > 0 ? (uint64_t)nsl_hint : 1;
-        const uint64_t tall = ((uint64_t)p.nrows + geo.NW * geo.KA - 1) / (geo.NW * geo.KA), wgs = tall * nsl;
-        uint32_t S = 1;
-        if (g_tune.lds_col_split > 1) S = (uint32_t)std::min<int64_t>(g_tune.lds_col_split, 16);
-        else if (wgs * 2 <= cus) S = (uint32_t)std::min<uint64_t>(8, cus / wgs);
-        // Round 6: a share whose rows ALL BUT fit tall' x slices x S' = one workgroup per compute unit for a larger S' (29 471 rows: 16 full tiles x 4 slices x 4
-        // ranges = 256 workgroups hold 29 184 of them, against 17 x 4 x 3 = 204 for all) keeps its last few rows out of the plan: k_lds_tail takes them from the
-        // same staged copy (launch_lds).  4-byte element types, unit weights, plans written by the device or the host encoder alike (they see fewer rows).
-        if (g_tune.lds_col_split == 0 && g_tune.lds_row_tail > 0 && want_code && es == 4 && !p.lds_forced && (uint64_t)p.nrows * 8 < (1ull << 31)) {
-            const uint64_t full = (uint64_t)geo.NW * geo.KA;
-            for (uint32_t S2 = 8; S2 > S; S2--) {
-                const uint64_t tall2 = cus / (nsl * S2);
-                if (!tall2) continue;
-                const uint64_t covered = tall2 * full;
-                if (covered >= (uint64_t)p.nrows) break;   // (S itself would be at least S2)
-                if (((uint64_t)p.nrows - covered) * 100 <= (uint64_t)p.nrows * (uint64_t)g_tune.lds_row_tail && tall2 * nsl * S2 * 10 >= (uint64_t)cus * 9) {
-                    S = S2;
-                    rows_lds = (uint32_t)covered;
-                    break;
-                }
-            }
-        }
-        if (S > 1 && (uint64_t)p.nrows * S < (1ull << 31)) {
-            geo.col_splits = S;
-            geo.rows_per_tile = 0;   // full-height tiles: the column ranges fill the chip
-            // one round of workgroups: nothing to gain from heaviest-first, and in their natural order (row tile x S + range) the launch's XCD interleave
-            // (tile t on XCD set t mod G, G = 4 or 8) hands an XCD the tiles of ONE column range when S is 2, 4 or 8 -- its L2 then streams one range per
-            // slice for 16 row tiles instead of every range for four (0.64 -> 0.57 us per chunk on a 1/8 share, profiles/r06_stamps.txt)
-            if (g_tune.lds_split_order && (((uint64_t)rows_lds + geo.NW * geo.KA - 1) / (geo.NW * geo.KA)) * nsl * S <= cus) geo.keep_tile_order = 1;
-            // ... and when tall x slices x S still leaves compute units without a workgroup (17 tall tiles x 4 slices x 3 ranges = 204 of 256), MORE,
-            // lighter row tiles for the same S: every workgroup streams the same N / S columns either way, with fewer entries per chunk
-            // (the stamps of profiles/r06_stamps.txt: 26 % of the CU-time of that launch was idle; one round only -- workgroups of a later round
-            // would stream their chunks out of step with the others and miss them in the L2)
-            if (g_tune.lds_col_split == 0 && g_tune.lds_fill_tiles && rows_lds == (uint32_t)p.nrows) {
-                const uint64_t tall2 = cus / (nsl * S);
-                if (tall2 > tall && tall2 <= 2 * tall) geo.rows_per_tile = (uint32_t)std::max<uint64_t>(16, ((uint64_t)p.nrows + tall2 - 1) / tall2);
-            }
+    struct FreeVals { uint32_t *q; ~FreeVals() { if (q) (void)hipFree(q); } } free_vals{d_vals32};
+    g_cg_fail_big_alloc = (g_tune.lds_fail & 8) != 0;
+    const std::string why = (p.vals && val_es < 4 && !d_vals32) ? std::string("out of device memory for the widened values") :
+              cg_run_on_device(p.rowptr, p.colind, es == 8 ? nullptr : (p.vals && val_es < 4) ? d_vals32 : (const uint32_t *)p.vals, es == 8 ? (const uint64_t *)p.vals : nullptr, h_rowptr.data(), ro, f.rows_lds,
+                               ncols_plan, f.geo, f.code_op,
+                               (uint32_t)std::max<int64_t>(0, g_tune.lds_code_gsize), (uint32_t)std::max<int64_t>(0, g_tune.lds_code_nsets), st, alloc_exec,
+                               free_exec, dr, [] { return now_ms(); }, f.half_H);
+    if (!why.empty()) return why;
+    if (lap.on)
+        fprintf(stderr, "[pygim plan] device code generation: rows %.1f, chunk lists %.1f, keys + sort %.1f, columns %.1f, slots + groups %.1f, sizes %.1f, emission %.1f, "
+                        "whole %.1f ms (%.1f MB of code)\n", dr.ms[0], dr.ms[1], dr.ms[2], dr.ms[3], dr.ms[4], dr.ms[5], dr.ms[6], dr.ms[7], dr.code_bytes / 1e6);
+    b.code = dr.code;
+    b.code_bytes = dr.code_bytes;
+    b.d_start = dr.d_start;
+    b.d_rowmap = dr.d_rowmap;
+    b.d_tiles = dr.d_tiles;
+    b.pairs = dr.pairs;
+    b.shared = dr.shared;
+    b.gsize = dr.regs.gsize;
+    b.nsets = dr.regs.nsets;
+    b.ntiles = dr.ntiles;
+    b.slots = dr.slots;
+    b.tokens = dr.entries;
+    b.device = true;
+    if (g_tune.lds_codegen == 2) {   // the checker: the host encoder's blob against what the device wrote
+        const std::string diff = codegen_verify(p, f.geo, f.code_op, h_rowptr, ro, dr, d_vals32, f.rows_lds, f.half_H);
+        if (!diff.empty()) {
+            b.release();
+            b = LdsBuilt();
+            rc = fail(PYGIM_ERR_INVALID, ("lds_codegen = 2: the device-generated code stream differs from the host encoder's: " + diff).c_str());
         }
     }
-    if (want_code) {
-        // the ring.  Two buffers of 320 columns: the workgroup meets at every slot boundary (round 3).  Three or more (round 4): one
-        // barrier in the middle of a slot, NBUF - 2 chunks in flight beside the one being read, no drain at the boundary -- the DMA
-        // requests of a CU never dry up (scripts/micro/fillrate.hip: 81 GB/s per CU with 2 x 80 KiB, 113 GB/s with 3 x 48 or 4 x 40 KiB)
-        code_ring(geo.NW, geo.row_bytes, geo.NBUF, geo.KC);
-        // measured (profiles/r04_lds_kernel.md): with five buffers the boundary form -- four chunks in flight -- is 1-2 % ahead of the mid-slot form on
-        // every shape tried (2.02-2.04 against 2.06 ms on the bench workload, DBL64 7.03 against 7.12): the default
-        geo.boundary = g_tune.lds_code_boundary == 2 ? 0u : 1u;
-    }
-    // Round 6: HALF-SPLIT plans for products of 17..32 lanes (all rows x 32 FLT32 features: a feature-split rank).  A 64-lane slice would be half empty and every tile
-    // would still stage all of X in 256-byte rows; instead a staged row holds TWO columns' 32 lanes side by side ([X[c] | X[c + H]]: half the rows, half the
-    // staged bytes), the plan is made of the virtual columns c mod H with each entry's half in its value slot, the stream adds under the lower / upper half of
-    // EXEC and the store adds the two halves (lds_plan.hpp LdsGeometry::half_split, scripts/gen_lds_kernel.py).  A row's sum becomes (sum over the lower range)
-    // + (sum over the upper range): integers exact, FLT32 under the same rule as column-split tiles.  Written by the host encoder.
-    const int64_t lanes_hint = h_hint > 0 ? (h_hint * (int64_t)es + 3) / 4 : 0;
-    const bool half = want_code && g_tune.lds_half_split && es == 4 && geo.NW == 8 && !p.vals && !p.lds_forced && lanes_hint > 0 && lanes_hint <= 32 &&
-                      (t_plan_dtype == PYGIM_INT32 || (t_plan_dtype == PYGIM_FLT32 && f32_split_ok)) && rows_lds == (uint32_t)p.nrows && (uint64_t)p.ncols >= 4ull * geo.KC &&
-                      !g_tune.lds_code_exp && !(g_tune.lds_fail & 7);
-    uint32_t half_H = 0;
-    if (half) {
-        half_H = (uint32_t)(((((uint64_t)p.ncols + 1) / 2 + geo.KC - 1) / geo.KC) * geo.KC);
-        geo.half_split = 1;
-    }
-    // (products of at most 32 lanes gather fewer bytes per entry on the sweep: their plans must serve more entries per staged column to pay -- rt_state.inc)
-    const bool narrow_hint = es != 8 && lanes_hint > 0 && lanes_hint <= 32;
-    const double min_reuse_x100 = !narrow_hint ? (double)g_tune.lds_min_reuse_x100
-                                               : std::max((double)g_tune.lds_min_reuse_x100, (double)g_tune.lds_min_reuse_narrow_x100 * (half ? 1.6 : 1.0));
-    if (g_tune.lds_mode == 0 && !p.lds_forced &&
-        lds_plan_uniform_reuse((uint64_t)p.nnz, (uint32_t)p.nrows, half ? half_H : (uint32_t)p.ncols, geo) * 100.0 < min_reuse_x100)
-        return 0;
-    if (p.cols_sorted < 0) {  // (the panel plan may have asked already)
-        int unsorted = 0;
-        if (hipMemsetAsync(d_flag_sorted, 0, sizeof(int), st) != hipSuccess) return fail(PYGIM_ERR_HIP, "flag reset");
-        hipLaunchKernelGGL(k_check_sorted_cols, dim3((unsigned)((p.nrows + 255) / 256)), dim3(256), 0, st, p.rowptr, p.colind,
-                           (uint32_t)p.nrows, d_flag_sorted);
-        if (hipMemcpy(&unsorted, d_flag_sorted, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(PYGIM_ERR_HIP, "sortedness check");
-        p.cols_sorted = unsorted ? 0 : 1;
-    }
-    if (!p.cols_sorted) return 0;  // stored order inside a row must be column order for the chunk walk
-    const uint32_t code_op = t_plan_dtype == PYGIM_FLT32 ? 0x02000000u : t_plan_dtype == PYGIM_INT32 ? 0x68000000u : t_plan_dtype == PYGIM_DBL64 ? LDS_CODE_ADD_F64 :
-                             t_plan_dtype == PYGIM_INT64 ? LDS_CODE_ADD_U64 : LDS_CODE_PK_ADD_U16;
-    // Round 5: similarity tiles (lds_reorder_dev.hpp) -- rows with similar neighbourhoods share a tile: shared LDS reads, skipped chunks.
-    // The result does not depend on the order (each row is summed by one wave in stored order whichever tile holds it).
-    std::vector<uint32_t> rorder;
-    if (want_code && p.nrows == p.ncols && rows_lds == (uint32_t)p.nrows && !half &&
-        (g_tune.lds_tile_order == 1 || p.lds_forced || (g_tune.lds_tile_order == 2 && p.nnz >= (1 << 20)))) {
-        // automatic: ids that are local already (a row's columns span a small part of the id range: tiles of consecutive rows skip most
-        // chunks as they are) keep consecutive tiles; otherwise the propagation decides -- it must have found communities (more than
-        // one label, none holding half of the rows), else its order is the consecutive one anyway (profiles/r05_structured.txt)
-        find_similarity(p, st, g_tune.lds_tile_order == 1 || p.lds_forced);
-        if (p.sim_kind == 2) {
-            rorder = p.sim_order;
-            p.lds_tile_labels = p.sim_labels;
-            p.lds_tile_largest = p.sim_largest;
-        }
-        lap("similarity order (label propagation)");
-    }
-    const uint32_t *ro = rorder.empty() ? nullptr : rorder.data();
-    // Round 5: the code stream GENERATED ON THE DEVICE (lds_codegen_dev.hpp) from the resident CSR -- the same bytes the host encoder
-    // below would write (lds_codegen = 2 checks that, word for word) without the graph ever visiting the host.  Plans it does not
-    // cover (column-split tiles, the mid-slot hand-off, timing experiments), or a failure on the way, take the host encoder.
-    std::string dev_why;
-    if (want_code && g_tune.lds_codegen && !(g_tune.lds_fail & 7) && !g_tune.lds_code_exp) {
-        CgDeviceResult dr;
-        std::string exec_why;
-        auto alloc_exec = [&](size_t bytes) -> void * { return exec_alloc(bytes, &exec_why); };
-        auto free_exec = [&](void *q) { (void)hsa_amd_memory_pool_free(q); };
-        // (round 5: valued INT16 / INT8 -- the values sign-extended to the 4-byte slot the encoders read: v_pk_mul_lo_u16 takes the low half)
-        uint32_t *d_vals32 = nullptr;
-        if (p.vals && val_es < 4) {
-            if (hipMalloc((void **)&d_vals32, std::max<size_t>((size_t)p.nnz * 4, 256)) != hipSuccess) {
-                (void)hipGetLastError();
-                d_vals32 = nullptr;
-            } else if (val_es == 1) hipLaunchKernelGGL((k_widen_vals<int8_t>), dim3((unsigned)(((uint64_t)p.nnz + 255) / 256)), dim3(256), 0, st, (const int8_t *)p.vals, (uint64_t)p.nnz, d_vals32);
-            else hipLaunchKernelGGL((k_widen_vals<int16_t>), dim3((unsigned)(((uint64_t)p.nnz + 255) / 256)), dim3(256), 0, st, (const int16_t *)p.vals, (uint64_t)p.nnz, d_vals32);
-        }
-        struct FreeVals { uint32_t *q; ~FreeVals() { if (q) (void)hipFree(q); } } free_vals{d_vals32};
-        g_cg_fail_big_alloc = (g_tune.lds_fail & 8) != 0;
-        dev_why = (p.vals && val_es < 4 && !d_vals32) ? std::string("out of device memory for the widened values") :
-                  cg_run_on_device(p.rowptr, p.colind, es == 8 ? nullptr : (p.vals && val_es < 4) ? d_vals32 : (const uint32_t *)p.vals, es == 8 ? (const uint64_t *)p.vals : nullptr, h_rowptr.data(), ro, rows_lds,
-                                   half ? half_H : (uint32_t)p.ncols, geo, code_op,
-                                   (uint32_t)std::max<int64_t>(0, g_tune.lds_code_gsize), (uint32_t)std::max<int64_t>(0, g_tune.lds_code_nsets), st, alloc_exec,
-                                   free_exec, dr, [] { return now_ms(); }, half ? half_H : 0u);
-        if (dev_why.empty()) {
-            if (plan_timing)
-                fprintf(stderr, "[pygim plan] device code generation: rows %.1f, chunk lists %.1f, keys + sort %.1f, columns %.1f, slots + groups %.1f, sizes %.1f, emission %.1f, "
-                                "whole %.1f ms (%.1f MB of code)\n", dr.ms[0], dr.ms[1], dr.ms[2], dr.ms[3], dr.ms[4], dr.ms[5], dr.ms[6], dr.ms[7], dr.code_bytes / 1e6);
-            if (g_tune.lds_codegen == 2) {   // the checker: the host encoder's blob against what the device wrote
-                std::string diff = codegen_verify(p, geo, code_op, h_rowptr, ro, dr, d_vals32, rows_lds, half ? half_H : 0u);
-                if (!diff.empty()) {
-                    (void)hsa_amd_memory_pool_free(dr.code);
-                    (void)hipFree(dr.d_start);
-                    (void)hipFree(dr.d_rowmap);
-                    (void)hipFree(dr.d_tiles);
-                    return fail(PYGIM_ERR_INVALID, ("lds_codegen = 2: the device-generated code stream differs from the host encoder's: " + diff).c_str());
-                }
-            }
-            p.lds_code = (char *)dr.code;
-            p.lds_code_bytes = dr.code_bytes;
-            p.lds_code_start = dr.d_start;
-            p.lds_rowmap = dr.d_rowmap;
-            p.lds_tiles = dr.d_tiles;
-            p.lds_code_pairs = dr.pairs;
-            p.lds_code_shared = dr.shared;
-            p.lds_is_code = true;
-            p.lds_code_piece = geo.KC * geo.row_bytes / geo.NW;
-            p.lds_code_gsize = dr.regs.gsize;
-            p.lds_code_nsets = dr.regs.nsets;
-            p.lds_col_splits = geo.col_splits;
-            p.lds_kc = geo.KC;
-            p.lds_nbuf = geo.NBUF;
-            p.lds_row_bytes = geo.row_bytes;
-            p.lds_ka = geo.KA;
-            p.lds_ntiles = dr.ntiles;
-            p.lds_nw = geo.NW;
-            p.lds_batch = geo.BATCH;
-            p.lds_slots = dr.slots;
-            p.lds_tokens = dr.entries;   // (a code stream has no padding)
-            p.lds_codegen_device = true;
-            p.lds_rows = rows_lds < (uint32_t)p.nrows ? rows_lds : 0;
-            p.lds_half = half ? half_H : 0;
-            lap("code stream generated on the device");
-            return build_tail_segments(p, h_rowptr);
-        }
-        (void)hipGetLastError();
-        if (plan_timing) fprintf(stderr, "[pygim plan] device code generation not used: %s\n", dev_why.c_str());
-        p.lds_codegen_why = dev_why;
-    } else if (want_code) {
-        p.lds_codegen_why = !g_tune.lds_codegen ? "lds_codegen = 0" : (g_tune.lds_fail & 7) ? "lds_fail set" : "timing experiment";
-    }
+    return std::string();
+}
+
+// The host encoder: column ids (and values) to the host, the schedule (lds_plan_build), for a code stream its machine code into executable
+// memory, the tables to the device.  0 with b.d_tiles == nullptr: no plan (p.lds_note may say why); -1: the next rung of build_lds_plan's ladder.
+static int lds_plan_on_host(Part &p, const LdsForm &f, LdsGeometry &geo, size_t val_es, const std::vector<uint32_t> &h_rowptr, const uint32_t *ro, PlanLap &lap, LdsBuilt &b) {
+    const size_t es = f.es;
+    const bool want_code = f.want_code, half = f.half_H != 0;
+    const unsigned threads = (unsigned)std::max<int64_t>(0, g_tune.lds_threads);
     std::vector<uint32_t> h_col((size_t)p.nnz);
     if (hipMemcpy(h_col.data(), p.colind, h_col.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(PYGIM_ERR_HIP, "colind D2H");
     lap("sortedness check + column ids D2H");
@@ -761,42 +651,24 @@ static int build_lds_plan_form(Part &p, size_t es, int *d_flag_sorted, hipStream
     LdsPlanHost plan;
     try {
         if (g_tune.lds_fail & 4) throw std::runtime_error("lds_fail: forced failure of the schedule build");
-        if (half) half_split_virtual_matrix(h_rowptr, (uint32_t)p.nrows, half_H, h_col, h_val);
-        lds_plan_build(h_rowptr.data(), h_col.data(), rows_lds, half ? half_H : (uint32_t)p.ncols, geo, plan, (unsigned)std::max<int64_t>(0, g_tune.lds_threads),
-                       (p.vals || half) ? h_val.data() : nullptr, ro);
+        if (half) half_split_virtual_matrix(h_rowptr, (uint32_t)p.nrows, f.half_H, h_col, h_val);
+        lds_plan_build(h_rowptr.data(), h_col.data(), f.rows_lds, half ? f.half_H : (uint32_t)p.ncols, geo, plan, threads, (p.vals || half) ? h_val.data() : nullptr, ro);
+        lap("schedule (tiles, tokens)");
+        // long slots (lds_form.hpp): the 16-token-batch geometry for a schedule whose waves get this many tokens per slot
+        if (f.long_candidate && plan.slots > 0 && (double)plan.ntokens / ((double)plan.slots * geo.NW) >= (double)g_tune.lds_long_slots) {
+            lds_plan_build(h_rowptr.data(), h_col.data(), (uint32_t)p.nrows, (uint32_t)p.ncols, f.long_geo, plan, threads, nullptr);
+            geo = f.long_geo;
+        }
     } catch (const std::exception &e) {   // host memory, threads: no LDS-staged plan, the sweep serves the group
         p.lds_note = std::string("the schedule of the LDS-staged product could not be built (") + e.what() + "): the L2 sweep serves this group";
         return 0;
-    }
-    lap("schedule (tiles, tokens)");
-    // long slots (a community-structured graph: a tile streams few chunks, a wave gets hundreds of tokens per chunk): the per-batch
-    // bookkeeping is what is left to save -- the 16-token-batch geometry, when the tiles fit its 80 accumulators per wave
-    if (geo.NW == 16 && !p.vals && !want_code && g_tune.lds_long_slots && plan.slots > 0 &&
-        (double)plan.ntokens / ((double)plan.slots * geo.NW) >= (double)g_tune.lds_long_slots) {
-        LdsGeometry gl = geo;
-        gl.KA = LDS_L16_KA;
-        gl.BATCH = LDS_L16_BATCH;
-        gl.rows_per_tile = geo.col_splits > 1 ? 0 : g_tune.lds_round_tiles && h_hint > 0
-                               ? lds_rows_per_tile((uint32_t)p.nrows, gl.NW * gl.KA, (uint32_t)nsl_hint, (uint32_t)std::max(g_ctx.cu_count, 1))
-                               : 0;
-        const uint32_t r_now = geo.rows_per_tile ? geo.rows_per_tile : geo.NW * geo.KA, r_new = gl.rows_per_tile ? gl.rows_per_tile : gl.NW * gl.KA;
-        if (r_new >= r_now) {  // no more tiles than before
-            try {
-                lds_plan_build(h_rowptr.data(), h_col.data(), (uint32_t)p.nrows, (uint32_t)p.ncols, gl, plan,
-                               (unsigned)std::max<int64_t>(0, g_tune.lds_threads), nullptr);
-            } catch (const std::exception &e) {
-                p.lds_note = std::string("the schedule of the LDS-staged product could not be built (") + e.what() + "): the L2 sweep serves this group";
-                return 0;
-            }
-            geo = gl;
-        }
     }
     std::vector<uint32_t>().swap(h_col);
     std::vector<uint32_t>().swap(h_val);
     if (p.vals && !want_code) {
         // one buffer: the token stream, then the value stream at the same positions (the kernel adds a 32-bit byte offset)
         if ((uint64_t)plan.tok.size() * 8 >= (1ull << 32)) return 0;
-        p.lds_wdelta = (uint32_t)(plan.tok.size() * 4);
+        b.wdelta = (uint32_t)(plan.tok.size() * 4);
         plan.tok.insert(plan.tok.end(), plan.wts.begin(), plan.wts.end());
         std::vector<uint32_t>().swap(plan.wts);
     }
@@ -810,59 +682,118 @@ static int build_lds_plan_form(Part &p, size_t es, int *d_flag_sorted, hipStream
         p.lds_note = "the LDS-staged schedule does not fit its slot headers (more than 16 383 batches of one wave in one chunk, or more than 5 M columns): the L2 sweep serves this group";
         return 0;
     }
-    if (want_code) {
-        // the schedule as machine code (1.5 instructions per stored entry instead of 4 + bookkeeping) in EXECUTABLE memory; the token
-        // stream itself stays on the host (the kernel needs the tile table and the row map only)
-        LdsCodeHost ch;
-        try {
-            if (g_tune.lds_fail & 1) throw std::runtime_error("lds_fail: forced failure of the code generation");
-            lds_code_from_plan(plan, t_plan_dtype == PYGIM_FLT32 ? 0x02000000u : t_plan_dtype == PYGIM_INT32 ? 0x68000000u : t_plan_dtype == PYGIM_DBL64 ? LDS_CODE_ADD_F64 :
-                                     t_plan_dtype == PYGIM_INT64 ? LDS_CODE_ADD_U64 : LDS_CODE_PK_ADD_U16, ch,
-                               (unsigned)std::max<int64_t>(0, g_tune.lds_threads), (uint32_t)std::max<int64_t>(0, g_tune.lds_code_gsize),
-                               (uint32_t)std::max<int64_t>(0, g_tune.lds_code_nsets), (uint32_t)std::max<int64_t>(0, g_tune.lds_code_exp),
-                               h_val64.empty() ? nullptr : h_val64.data());
-        } catch (const std::exception &e) {   // out of host memory or threads: the same schedule as a token plan (build_lds_plan)
-            p.lds_note = std::string("code-stream form not available: generating the instruction streams failed (") + e.what() + ")";
-            return -1;
-        }
-        lap("code generation");
-        std::vector<uint32_t>().swap(plan.tok);
-        std::string why_exec;
-        void *code = (g_tune.lds_fail & 2) ? nullptr : exec_alloc_upload(ch.code.data(), ch.code.size() * 4, &why_exec);
-        if (!code) {                     // no executable pool on this runtime, or out of device memory: the token plan
-            p.lds_note = "code-stream form not available: " + (why_exec.empty() ? std::string("lds_fail: forced failure of the executable allocation") : why_exec) +
-                         " (" + std::to_string(ch.code.size() * 4) + " bytes of code)";
-            return -1;
-        }
-        if (!up(&p.lds_code_start, ch.start) || !up(&p.lds_rowmap, plan.rowmap) || !up(&p.lds_tiles, plan.tiles)) {
-            (void)hsa_amd_memory_pool_free(code);
-            return fail(PYGIM_ERR_HIP, "code-stream plan upload");
-        }
-        lap("code + tables upload");
-        p.lds_code = (char *)code;
-        p.lds_code_bytes = ch.code.size() * 4;
-        p.lds_code_pairs = ch.pairs;
-        p.lds_is_code = true;
-        p.lds_code_piece = geo.KC * geo.row_bytes / geo.NW;
-        p.lds_code_gsize = ch.regs.gsize;
-        p.lds_code_nsets = ch.regs.nsets;
-        p.lds_code_shared = ch.shared;
-    } else if (!up(&p.lds_tok, plan.tok) || !up(&p.lds_rowmap, plan.rowmap) || !up(&p.lds_tiles, plan.tiles)) {
+    b.ntiles = plan.ntiles;
+    b.slots = plan.slots;
+    b.tokens = plan.ntokens;
+    if (!want_code) {
+        if (up(&b.d_tok, plan.tok) && up(&b.d_rowmap, plan.rowmap) && up(&b.d_tiles, plan.tiles)) return 0;
+        b.release();
+        b = LdsBuilt();
         return fail(PYGIM_ERR_HIP, "LDS plan upload");
     }
-    p.lds_col_splits = geo.col_splits;
-    p.lds_rows = rows_lds < (uint32_t)p.nrows ? rows_lds : 0;
-    p.lds_half = half ? half_H : 0;
-    p.lds_kc = geo.KC;
-    p.lds_nbuf = geo.NBUF;
-    p.lds_row_bytes = geo.row_bytes;
-    p.lds_ka = geo.KA;
-    p.lds_ntiles = plan.ntiles;
-    p.lds_nw = geo.NW;
-    p.lds_batch = geo.BATCH;
-    p.lds_slots = plan.slots;
-    p.lds_tokens = plan.ntokens;
-    return build_tail_segments(p, h_rowptr);
+    // the schedule as machine code (1.5 instructions per stored entry instead of 4 + bookkeeping) in EXECUTABLE memory; the token
+    // stream itself stays on the host (the kernel needs the tile table and the row map only)
+    LdsCodeHost ch;
+    try {
+        if (g_tune.lds_fail & 1) throw std::runtime_error("lds_fail: forced failure of the code generation");
+        lds_code_from_plan(plan, f.code_op, ch, threads, (uint32_t)std::max<int64_t>(0, g_tune.lds_code_gsize), (uint32_t)std::max<int64_t>(0, g_tune.lds_code_nsets),
+                           (uint32_t)std::max<int64_t>(0, g_tune.lds_code_exp), h_val64.empty() ? nullptr : h_val64.data());
+    } catch (const std::exception &e) {   // out of host memory or threads: the same schedule as a token plan (build_lds_plan)
+        p.lds_note = std::string("code-stream form not available: generating the instruction streams failed (") + e.what() + ")";
+        return -1;
+    }
+    lap("code generation");
+    std::vector<uint32_t>().swap(plan.tok);
+    std::string why_exec;
+    b.code = (g_tune.lds_fail & 2) ? nullptr : exec_alloc_upload(ch.code.data(), ch.code.size() * 4, &why_exec);
+    if (!b.code) {                     // no executable pool on this runtime, or out of device memory: the token plan
+        p.lds_note = "code-stream form not available: " + (why_exec.empty() ? std::string("lds_fail: forced failure of the executable allocation") : why_exec) +
+                     " (" + std::to_string(ch.code.size() * 4) + " bytes of code)";
+        return -1;
+    }
+    if (!up(&b.d_start, ch.start) || !up(&b.d_rowmap, plan.rowmap) || !up(&b.d_tiles, plan.tiles)) {
+        b.release();
+        b = LdsBuilt();
+        return fail(PYGIM_ERR_HIP, "code-stream plan upload");
+    }
+    lap("code + tables upload");
+    b.code_bytes = ch.code.size() * 4;
+    b.pairs = ch.pairs;
+    b.shared = ch.shared;
+    b.gsize = ch.regs.gsize;
+    b.nsets = ch.regs.nsets;
+    return 0;
+}
+
+// One form of the LDS-staged plan of a part: choose it (lds_form.hpp: a pure function), ask the device what the choice cannot know,
+// let the device generator or the host encoder build it, adopt what they made.  0 without p.lds_tiles: no plan; -1: the next rung.
+static int build_lds_plan_form(Part &p, size_t val_es, int *d_flag_sorted, hipStream_t st, const std::vector<uint32_t> &h_rowptr, int64_t h_hint,
+                               bool allow_code) {
+    PlanLap lap;
+    LdsFormInput in;
+    in.dtype = t_plan_dtype;
+    in.val_es = val_es;
+    in.nrows = p.nrows;
+    in.ncols = p.ncols;
+    in.nnz = p.nnz;
+    in.valued = p.vals != nullptr;
+    in.is_extra = p.is_extra;
+    in.lds_forced = p.lds_forced;
+    in.lds_contig_tiles = p.lds_contig_tiles;
+    in.h_hint = h_hint;
+    in.cu_count = g_ctx.cu_count;
+    in.allow_code = allow_code;
+    in.k.kc = LDS_KC;
+    in.k.lds_bytes = LDS_BYTES;
+    in.k.ka8 = lds_ka(8);
+    in.k.batch8 = lds_batch(8);
+    in.k.ka16 = lds_ka(16);
+    in.k.batch16 = lds_batch(16);
+    in.k.l16_ka = LDS_L16_KA;
+    in.k.l16_batch = LDS_L16_BATCH;
+    const LdsForm f = lds_choose_form(in, lds_form_knobs());
+    if (!f.plan) return 0;
+    if (p.cols_sorted < 0) {  // (the panel plan may have asked already)
+        int unsorted = 0;
+        if (hipMemsetAsync(d_flag_sorted, 0, sizeof(int), st) != hipSuccess) return fail(PYGIM_ERR_HIP, "flag reset");
+        hipLaunchKernelGGL(k_check_sorted_cols, dim3((unsigned)((p.nrows + 255) / 256)), dim3(256), 0, st, p.rowptr, p.colind,
+                           (uint32_t)p.nrows, d_flag_sorted);
+        if (hipMemcpy(&unsorted, d_flag_sorted, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(PYGIM_ERR_HIP, "sortedness check");
+        p.cols_sorted = unsorted ? 0 : 1;
+    }
+    if (!p.cols_sorted) return 0;  // stored order inside a row must be column order for the chunk walk
+    std::vector<uint32_t> rorder;
+    if (f.want_similarity) {
+        // automatic: ids that are local already (a row's columns span a small part of the id range: tiles of consecutive rows skip most
+        // chunks as they are) keep consecutive tiles; otherwise the propagation decides -- it must have found communities (more than
+        // one label, none holding half of the rows), else its order is the consecutive one anyway (profiles/r05_structured.txt)
+        find_similarity(p, st, f.similarity_forced);
+        if (p.sim_kind == 2) {
+            rorder = p.sim_order;
+            p.lds_tile_labels = p.sim_labels;
+            p.lds_tile_largest = p.sim_largest;
+        }
+        lap("similarity order (label propagation)");
+    }
+    const uint32_t *ro = rorder.empty() ? nullptr : rorder.data();
+    LdsBuilt b;
+    LdsGeometry geo = f.geo;   // (the host encoder may take the long-slots geometry instead)
+    if (f.device_codegen) {    // plans the device generator does not cover, or a failure on the way, take the host encoder
+        int rc = 0;
+        const std::string dev_why = lds_plan_on_device(p, f, val_es, st, h_rowptr, ro, lap, b, rc);
+        if (rc) return rc;
+        if (dev_why.empty()) {
+            lap("code stream generated on the device");
+            return adopt_lds_plan(p, f, geo, b, h_rowptr);
+        }
+        (void)hipGetLastError();
+        if (lap.on) fprintf(stderr, "[pygim plan] device code generation not used: %s\n", dev_why.c_str());
+        p.lds_codegen_why = dev_why;
+    } else if (f.want_code) {
+        p.lds_codegen_why = f.codegen_why;
+    }
+    if (int rc = lds_plan_on_host(p, f, geo, val_es, h_rowptr, ro, lap, b)) return rc;
+    return b.d_tiles ? adopt_lds_plan(p, f, geo, b, h_rowptr) : 0;
 }
 
 double now_ms() {
