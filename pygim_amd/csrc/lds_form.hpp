@@ -96,7 +96,7 @@ inline LdsForm lds_choose_form(const LdsFormInput &in, const LdsFormKnobs &t) {
     if (es == 8 && !el8_code) return f;
     if (t.lds_mode == 2 || (es != 4 && es != 2 && es != 8) || in.is_extra || in.nnz == 0 || in.nrows == 0 || in.ncols == 0) return f;
     if ((in.valued || es == 2) && t.lds_waves != 16) return f;  // the valued and the INT16 kernels exist for the 16-wave geometry
-    // no product of this group is wide enough (want_lds; INT8 rides the INT16 stream: lanes of two features): no plan, no code
+    // no product of this group is wide enough (lds_launch.hpp lds_takes; INT8 rides the INT16 stream: lanes of two features): no plan, no code
     if (in.h_hint > 0 && (es == 8 ? in.h_hint : (in.h_hint * (int64_t)std::max<size_t>(es, 2)) / 4) < (es == 8 ? t.lds_min_width8 : t.lds_min_width)) return f;
     if ((uint64_t)in.ncols * (es == 8 ? 512ull : 256ull) >= (1ull << 32) - (1ull << 20) || (uint64_t)in.nnz >= (1ull << 31)) return f;
     const uint32_t nrows = (uint32_t)in.nrows, ncols = (uint32_t)in.ncols;

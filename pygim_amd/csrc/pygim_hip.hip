@@ -17,11 +17,12 @@
 #include "lds_kernel_gen_ablate.hpp"   // (make ablate: the same kernels + round 3's timing-experiment variants; not committed)
 #else
 #include "lds_kernel_gen.hpp"
+#endif
 #include "lds_codegen_dev.hpp"
 #include "lds_reorder_dev.hpp"
 #include "lds_hybrid_dev.hpp"
-#endif
 #include "lds_form.hpp"
+#include "lds_launch.hpp"
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
 #include "row_gather_dev.hpp"
@@ -33,15 +34,6 @@
 #include "spmm_multi_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
-
-// rows of a slice of the slice-major copy: whole chunks of either kernel family (320-column chunks of the token kernels, 192 of the
-// code-stream kernels), so that the DMA of a tile's last chunk stays inside the copy
-// rows of a slice of the staged copy: whole chunks of the part's ring (the DMA of a tile's last chunk reads KC rows whatever the
-// matrix's width), 64-row aligned
-static inline uint64_t lds_rows_pad(uint64_t ncols, uint32_t kc) {
-    const uint64_t k = kc ? kc : 320;
-    return ((ncols + k - 1) / k * k + 63) / 64 * 64;
-}
 
 #include <algorithm>
 #include <atomic>
@@ -66,6 +58,9 @@ namespace {
 }  // namespace
 
 #include "rt_run.inc"
+
+// the part whose plans the group's queries report: the merged matrix when it serves the products, else part 0
+static const Part &serving_part(const Group *g) { return (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0]; }
 
 // ===========================================================================
 // C ABI
@@ -1180,7 +1175,7 @@ int pygim_group_kernel_events(int64_t handle, int on) {
 int pygim_group_plan(int64_t handle, int64_t out[8]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
-    const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
+    const Part &p = serving_part(g);
     int64_t ncoop = 0;
     for (auto c : p.panel_coop) ncoop += c;
     out[0] = p.d_items ? (int64_t)p.npanels : 0;
@@ -1197,7 +1192,7 @@ int pygim_group_plan(int64_t handle, int64_t out[8]) {
 int pygim_group_lds_plan(int64_t handle, int64_t out[4]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
-    const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
+    const Part &p = serving_part(g);
     out[0] = p.lds_tiles ? (int64_t)p.lds_ntiles : 0;
     out[1] = (int64_t)p.lds_slots;
     out[2] = (int64_t)p.lds_tokens;
@@ -1208,7 +1203,7 @@ int pygim_group_lds_plan(int64_t handle, int64_t out[4]) {
 int pygim_group_lds_code(int64_t handle, int64_t out[4]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
-    const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
+    const Part &p = serving_part(g);
     out[0] = p.lds_code ? (int64_t)p.lds_code_bytes : 0;
     out[1] = p.lds_code ? (int64_t)p.lds_code_pairs : 0;
     bool all_code = p.lds_is_code && g_tune.lds_code;
@@ -1222,7 +1217,7 @@ int pygim_group_lds_code(int64_t handle, int64_t out[4]) {
 int pygim_group_lds_tiles(int64_t handle, int64_t out[4]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
-    const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
+    const Part &p = serving_part(g);
     out[0] = p.lds_tile_labels ? 1 : 0;
     out[1] = p.lds_tile_labels;
     out[2] = p.lds_tile_largest;
@@ -1255,7 +1250,7 @@ int pygim_group_host_windows(int64_t handle, int64_t *windows, int64_t *direct) 
 int pygim_group_lds_geometry(int64_t handle, int64_t out[10]) {
     Group *g = lookup(handle);
     if (!g) return fail(PYGIM_ERR_INVALID, "unknown group handle");
-    const Part &p = (g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0];
+    const Part &p = serving_part(g);
     for (int i = 0; i < 10; i++) out[i] = 0;
     if (!p.lds_tiles) return 0;
     out[0] = p.lds_nw;
@@ -1267,10 +1262,9 @@ int pygim_group_lds_geometry(int64_t handle, int64_t out[10]) {
     out[6] = p.lds_is_code ? (int64_t)p.lds_code_shared : 0;
     out[7] = p.lds_col_splits;
     // a product of the group's full width, as launch_lds lays it over the XCDs under the tunables of this moment
-    const size_t es = dtype_size(g->dtype);
-    const uint32_t eps = es == 1 ? 128u : (uint32_t)((es == 8 ? 512 : 256) / std::max<size_t>(es, 1));
-    const uint32_t nslices = p.lds_half ? 1u : (uint32_t)((std::max<int64_t>(g->h, 1) + eps - 1) / eps);
-    const LdsXcdLayout lay = lds_xcd_layout(p, nslices, es == 8);
+    const size_t es = lds_el_bytes(g->dtype);
+    const LdsStaged xs = lds_staged(es, es == 1, (uint32_t)std::max<int64_t>(g->h, 1), (uint64_t)p.ncols, p.lds_kc, p.lds_half);
+    const LdsXcdLayout lay = lds_xcd_layout(lds_part_plan(p), xs.nslices, es == 8, lds_launch_knobs());
     out[8] = lay.sx;
     out[9] = lay.touch_share;
     return 0;
@@ -1284,7 +1278,7 @@ int pygim_group_lds_note(int64_t handle, char *out, int64_t cap) {
     // took a lower rung of the ladder than part 0 is named too (nothing falls back silently)
     std::string text;
     if ((g->merged && g_tune.merge_parts && g->parts.size() > 1) || g->parts.size() == 1) {
-        text = ((g->merged && g_tune.merge_parts && g->parts.size() > 1) ? *g->merged : g->parts[0]).lds_note;
+        text = serving_part(g).lds_note;
     } else {
         text = g->parts[0].lds_note;
         for (size_t i = 1; i < g->parts.size(); i++)

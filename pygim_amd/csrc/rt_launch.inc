@@ -1,5 +1,5 @@
 // rt_launch.inc -- part of pygim_hip.hip (inside its anonymous namespace): one block product -> kernels.  The sweep (launch_block_t), the LDS-staged
-// product in its token and code-stream forms (launch_lds, want_lds), the dispatch by element type.
+// product in its token and code-stream forms (launch_lds; its rules are lds_launch.hpp's), the dispatch by element type.
 // ---------------------------------------------------------------------------
 // launch plan for one block product
 // ---------------------------------------------------------------------------
@@ -281,42 +281,134 @@ int launch_block_t(Group *g, Part &p, const T *X, int64_t ldx, T *C, int64_t ldc
     return join();
 }
 
-// How a launch of the LDS-staged kernel lays its workgroups over the XCDs: group = XCDs that share the tiles of one set of slices (0 = no
-// XCD mapping: slice counts that do not divide 8), sx = slices per XCD, touch_share = the sx workgroups that run a tile's code streams side
-// by side share the touches (LdsArgs.touch_share).  One rule for the launch and for what pygim_group_lds_geometry reports.
-struct LdsXcdLayout {
-    uint32_t group = 0, sx = 1, touch_share = 0;
-};
-static LdsXcdLayout lds_xcd_layout(const Part &p, uint32_t nslices, bool el8) {
-    LdsXcdLayout l;
-    // (slice counts that do not divide 8 interleave the slices over the XCDs; a slice-major order measured the same: 2.86 vs 2.80 ms at h = 192)
-    l.group = (nslices == 1 || nslices == 2 || nslices == 4 || nslices == 8) ? 8 / nslices : 0;
-    // round 5 (VERDICT r04 item 3): sx slices per XCD -- the workgroups an XCD runs side by side are then the sx slices of ONE tile and
-    // share its code stream in that XCD's L2 (fetched from the fabric nslices / sx times instead of nslices), at the price of sx
-    // slices of X streamed through every L2 instead of one
-    if (l.group && p.lds_is_code && nslices > 1) {
-        // 0 = automatic (profiles/r05_exp_xcd.txt): two slices per XCD -- fabric traffic 5.28 -> 4.19 GB on the bench workload --
-        // and all (up to four) of them for plans whose tiles skip most chunks (little of X to un-share): 5.57 -> 3.72 GB, 1.05 -> 0.98 ms
-        uint32_t sx = (uint32_t)std::max<int64_t>(0, g_tune.lds_xcd_slices);
-        if (sx == 0) {
-            const uint64_t nchunks = ((uint64_t)p.ncols + p.lds_kc - 1) / std::max(1u, p.lds_kc);
-            const double fill = p.lds_ntiles && nchunks ? (double)p.lds_slots / ((double)p.lds_ntiles * (double)nchunks) : 1.0;
-            sx = fill < 0.3 ? std::min(nslices, 4u) : (el8 ? 1u : 2u);   // (8-byte rows: one slice per XCD measured 1 % ahead, 7.05-7.13 against 7.17-7.18 ms)
-            // (plans that stream every chunk, with the touches shared -- profiles/exp_touch_share.txt, bench workload: two slices 2.04 -> 1.97 ms, four 2.10 -> 1.99:
-            // the pair stays the fastest arrangement, the second pair's slices of X cost more than its touches save)
+// The tunables the launch rules read (lds_launch.hpp) and the plan fields of a Part, each copied in this one place.
+static LdsLaunchKnobs lds_launch_knobs() {
+    LdsLaunchKnobs k;
+#define PYGIM_KNOB(name) k.name = g_tune.name
+    PYGIM_KNOB(lds_xcd_slices); PYGIM_KNOB(lds_touch_share); PYGIM_KNOB(lds_code); PYGIM_KNOB(lds_ablate); PYGIM_KNOB(lds_mode); PYGIM_KNOB(lds_min_width);
+    PYGIM_KNOB(lds_min_width8); PYGIM_KNOB(panel_mode); PYGIM_KNOB(csr_kernel); PYGIM_KNOB(force_vec_bytes); PYGIM_KNOB(lds_direct_x);
+#undef PYGIM_KNOB
+    return k;
+}
+static LdsPartPlan lds_part_plan(const Part &p) {
+    LdsPartPlan q;
+    q.has_plan = p.lds_tiles != nullptr; q.is_code = p.lds_is_code; q.valued = p.vals != nullptr; q.wdelta = p.lds_wdelta != 0;
+    q.contig_tiles = p.lds_contig_tiles; q.col_order = p.lds_col_order != nullptr; q.tail_tables = p.lds_tail_segs && p.lds_tail_rowseg;
+    q.nw = p.lds_nw; q.batch = p.lds_batch; q.kc = p.lds_kc; q.row_bytes = p.lds_row_bytes; q.col_splits = p.lds_col_splits; q.half = p.lds_half;
+    q.rows = p.lds_rows; q.ntiles = p.lds_ntiles; q.tail_nseg = p.lds_tail_nseg; q.code_gsize = p.lds_code_gsize; q.code_nsets = p.lds_code_nsets;
+    q.slots = p.lds_slots; q.nrows = p.nrows; q.ncols = p.ncols;
+    return q;
+}
+
+// does launch_block hand this product to the LDS-staged kernel (lds_launch.hpp lds_takes)
+static bool lds_takes(const Group *g, const Part &p, uint32_t w, int64_t ldc, const void *C, bool accumulate = false) {
+    return lds_takes(g->dtype, lds_part_plan(p), w, ldc, (uintptr_t)C, accumulate, g->deq_out || g->pre_xs, lds_launch_knobs());
+}
+
+// The staged copy of X that a launch reads (lds_launch.hpp lds_staged): the caller's matrix in place when it IS the slice-major form, else a
+// copy of the same matrix made earlier when the caller says X is unchanged, else a fresh pack into the buffer of (device, stream).
+template <typename T>
+static int lds_stage_x(Group *g, const Part &p, const LdsStaged &xs, bool in_place, const T *X, int64_t ldx, uint32_t w, hipStream_t st, XsPin &pin, const void **out) {
+    // in_place (lds_plan_launch): the caller's matrix IS the slice-major form.  The last chunk's rows beyond the matrix are read too (never used): they must lie
+    // inside the caller's allocation.
+    if (in_place) {
+        void *base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)X) == hipSuccess && base && (const char *)X + xs.slice_stride <= (const char *)base + size) {
+            *out = X;
+            return 0;
         }
-        if (sx > 1 && sx <= nslices && nslices % sx == 0) {
-            l.sx = sx;
-            l.group *= sx;
+        (void)hipGetLastError();
+    }
+    Context::XsKey key;
+    key.src = X; key.ld = ldx; key.rows = p.ncols; key.w = (int64_t)w; key.order = p.lds_col_order; key.rows_pad = xs.rows_pad; key.es = sizeof(T); key.kind = xs.kind;
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    if (g->x_unchanged) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        Context::XsBuf *hit = nullptr;
+        for (auto &kv : g_ctx.xs_bufs) {
+            Context::XsBuf &b = kv.second;
+            // (the padded row count depends on the part's chunk size: a copy made for another ring geometry has another slice stride)
+            if (kv.first.first == dev && b.ptr && (const Context::XsKey &)b == key && b.bytes >= xs.bytes && (!hit || b.stamp > hit->stamp)) hit = &b;
+        }
+        if (hit) {
+            hit->stamp = ++g_ctx.xs_clock;
+            hit->in_use++;
+            pin.hold(hit->ptr);
+            *out = hit->ptr;
+            return 0;
         }
     }
-    // the partners of a toucher ask for one dword per touch instead of eight lines (L1 -> L2 read requests of the bench workload 271.5 M -> 257.0 M per product,
-    // 2.04 -> 1.97 ms): only the 8-wave shells set the touch register per workgroup, and only plans whose x registers leave it free touch through it
-    // (lds_plan.hpp lds_code_regs)
-    if (l.sx > 1 && g_tune.lds_touch_share && p.lds_is_code && p.lds_nw == 8 &&
-        lds_code_touch_shareable(lds_code_regs(8, p.lds_code_gsize, p.lds_code_nsets, p.lds_row_bytes == 512)))
-        l.touch_share = 1;
-    return l;
+    Context::XsBuf *b = nullptr;
+    if (int rc = xs_buffer_locked(st, std::max<size_t>(xs.bytes, 256), &b)) return rc;
+    pin.hold(b->ptr);
+    *out = b->ptr;
+    (Context::XsKey &)*b = key;
+    const uint32_t ncols = (uint32_t)p.ncols, rows_pad = (uint32_t)xs.rows_pad;
+    const uint32_t *order = (const uint32_t *)p.lds_col_order;
+    // a thread per 16-byte piece of a staged row (half-split: of every padded row)
+    const uint64_t threads = xs.kind == 5 ? xs.rows_pad * 16 : (uint64_t)p.ncols * xs.nslices * (xs.row_bytes / 16);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (xs.kind == 5) {
+        if constexpr (sizeof(T) == 4) hipLaunchKernelGGL((k_slice_pack_hs<T>), grid, dim3(256), 0, st, X, ldx, ncols, w, rows_pad, (T *)b->ptr);
+    } else if (threads > 0) {
+        if constexpr (sizeof(T) == 1)
+            hipLaunchKernelGGL(k_slice_pack_widen8, grid, dim3(256), 0, st, (const int8_t *)X, ldx, ncols, w, xs.nslices, (int16_t *)b->ptr, rows_pad, order);
+        else if constexpr (sizeof(T) == 8)
+            hipLaunchKernelGGL((k_slice_pack<T, 2, 5>), grid, dim3(256), 0, st, X, ldx, ncols, w, xs.nslices, (T *)b->ptr, rows_pad, order);   // 32 pieces per 512-byte row
+        else
+            hipLaunchKernelGGL((k_slice_pack<T, 16 / (int)sizeof(T), 4>), grid, dim3(256), 0, st, X, ldx, ncols, w, xs.nslices, (T *)b->ptr, rows_pad, order);
+    }
+    return 0;
+}
+
+// the kernels of the LDS-staged product by what lds_plan_launch asks for
+using LdsKernelFn = void (*)(LdsArgs);
+static LdsKernelFn lds_kernel_fn(const LdsKernelId &k) {
+    static const struct { uint32_t key; LdsKernelFn fn; } table[] = {
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_DBL64), k_lds_code8_f64},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT64), k_lds_code8_i64},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT8), k_lds_code8_i8},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT8, true), k_lds_code8_i8_deq},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT16), k_lds_code8_i16},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT16, true), k_lds_code8_i16_deq},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_FLT32), k_lds_code8_f32},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_FLT32, true), k_lds_code8_f32_deq},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_FLT32, false, true), k_lds_code8_f32_ts},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT32), k_lds_code8_i32},
+        {lds_kernel_key(LDS_SH_CODE8, LDS_EL_INT32, true), k_lds_code8_i32_deq},
+        {lds_kernel_key(LDS_SH_CODE16, LDS_EL_INT16), k_lds_code_i16},
+        {lds_kernel_key(LDS_SH_CODE16, LDS_EL_FLT32), k_lds_code_f32},
+        {lds_kernel_key(LDS_SH_CODE16, LDS_EL_FLT32, true), k_lds_code_f32_deq},
+        {lds_kernel_key(LDS_SH_CODE16, LDS_EL_INT32), k_lds_code_i32},
+        {lds_kernel_key(LDS_SH_CODE16, LDS_EL_INT32, true), k_lds_code_i32_deq},
+        {lds_kernel_key(LDS_SH_W16, LDS_EL_INT16), k_lds_spmm_i16_w16},
+        {lds_kernel_key(LDS_SH_W16B, LDS_EL_INT16), k_lds_spmm_i16_w16b},
+        {lds_kernel_key(LDS_SH_W16_VAL, LDS_EL_INT16), k_lds_spmm_i16_w16_val},
+        {lds_kernel_key(LDS_SH_W16, LDS_EL_FLT32), k_lds_spmm_f32_w16},
+        {lds_kernel_key(LDS_SH_W16, LDS_EL_FLT32, true), k_lds_spmm_f32_w16_deq},
+        {lds_kernel_key(LDS_SH_W16B, LDS_EL_FLT32), k_lds_spmm_f32_w16b},
+        {lds_kernel_key(LDS_SH_W16B, LDS_EL_FLT32, true), k_lds_spmm_f32_w16b_deq},
+        {lds_kernel_key(LDS_SH_W16_VAL, LDS_EL_FLT32), k_lds_spmm_f32_w16_val},
+        {lds_kernel_key(LDS_SH_W8, LDS_EL_FLT32), k_lds_spmm_f32_w8},
+        {lds_kernel_key(LDS_SH_W16, LDS_EL_INT32), k_lds_spmm_i32_w16},
+        {lds_kernel_key(LDS_SH_W16, LDS_EL_INT32, true), k_lds_spmm_i32_w16_deq},
+        {lds_kernel_key(LDS_SH_W16B, LDS_EL_INT32), k_lds_spmm_i32_w16b},
+        {lds_kernel_key(LDS_SH_W16B, LDS_EL_INT32, true), k_lds_spmm_i32_w16b_deq},
+        {lds_kernel_key(LDS_SH_W16_VAL, LDS_EL_INT32), k_lds_spmm_i32_w16_val},
+        {lds_kernel_key(LDS_SH_W8, LDS_EL_INT32), k_lds_spmm_i32_w8},
+#ifdef PYGIM_LDS_ABLATE
+        // timing experiments (wrong results, scripts/gen_lds_kernel.py; make ablate); an lds_ablate without a variant runs the kernel itself
+#define PYGIM_AB(n) {lds_kernel_key(LDS_SH_W16, LDS_EL_FLT32, false, false, n), k_lds_spmm_f32_w16_ab##n}
+        PYGIM_AB(6), PYGIM_AB(7), PYGIM_AB(10), PYGIM_AB(11), PYGIM_AB(12), PYGIM_AB(15), PYGIM_AB(16), PYGIM_AB(17), PYGIM_AB(18), PYGIM_AB(19),
+#undef PYGIM_AB
+#endif
+    };
+    for (const uint32_t key : {k.key(), lds_kernel_key(k.shell, k.el, k.deq, k.stamp)})
+        for (const auto &e : table)
+            if (e.key == key) return e.fn;
+    return nullptr;
 }
 
 // LDS-staged product (lds_kernel_gen.hpp / lds_plan.hpp): X is copied slice-major in 256-byte slices (64 features, rows padded to
@@ -327,204 +419,42 @@ static LdsXcdLayout lds_xcd_layout(const Part &p, uint32_t nslices, bool el8) {
 template <typename T>
 int launch_lds(Group *g, Part &p, const T *X, int64_t ldx, T *C, int64_t ldc, uint32_t w, bool accumulate, hipStream_t st,
                const void *lds_xs = nullptr, const uint32_t *deq_amax = nullptr, int deq_log2 = 0) {
-    constexpr bool WIDE8 = sizeof(T) == 1;                 // INT8: staged as INT16 (k_slice_pack_widen8), summed by the INT16 stream
-    constexpr bool EL8 = sizeof(T) == 8;                   // INT64 / DBL64: slices of 64 features = 512 bytes, a register pair per value
-    constexpr uint32_t ROWB = EL8 ? 512 : 256;             // bytes of a staged row
-    constexpr uint32_t EPS = WIDE8 ? 128 : ROWB / sizeof(T);   // elements of a slice
-    constexpr int PVEC = WIDE8 ? 8 : 16 / (int)sizeof(T);
-    // (INT8, and the dequantising INT16 store: the kernel masks features one by one; 8-byte: a lane = a feature)
-    // round 6: column-split plans of the 16-bit streams whose result is not the packed 16-bit sum itself (INT8 results, dequantised INT8 / INT16): the INT16 stream's
-    // plain kernel writes the ranges' packed partial sums, k_lds_reduce16 makes the result where they meet
-    const bool split16 = p.lds_col_splits > 1 && (WIDE8 || (sizeof(T) == 2 && deq_amax != nullptr));
-    const uint32_t w_lanes = split16 ? (uint32_t)(((size_t)w * 2 + 3) / 4)
-                                     : (WIDE8 || EL8 || (sizeof(T) == 2 && deq_amax)) ? w : (uint32_t)(((size_t)w * sizeof(T) + 3) / 4);
-    // half-split plans (round 6): ONE slice whose rows hold two columns' 32 lanes side by side, H = p.lds_half rows (a whole number of chunks)
-    const bool HS = p.lds_half != 0;
-    if (HS && (sizeof(T) != 4 || w > 32 || lds_xs || deq_amax)) return fail(PYGIM_ERR_INVALID, "internal: a half-split LDS plan serves plain 4-byte products of at most 32 lanes");
-    const uint32_t nslices = HS ? 1u : (w + EPS - 1) / EPS;
-    const uint64_t rows_pad = HS ? (uint64_t)p.lds_half : lds_rows_pad((uint64_t)p.ncols, p.lds_kc);
-    const size_t need = (size_t)rows_pad * nslices * ROWB;
+    // 1. the plan: everything that needs no device (lds_launch.hpp)
+    LdsLaunchInput in;
+    in.dtype = g->dtype; in.p = lds_part_plan(p); in.w = w; in.ldx = ldx; in.ldc = ldc; in.x_aligned256 = ((uintptr_t)X & 255) == 0; in.accumulate = accumulate; in.prestaged = lds_xs != nullptr; in.amax = deq_amax != nullptr;
+    in.c_aligned16 = ((uintptr_t)C & 15) == 0; in.stamp = g_tune.lds_stamp != 0; in.l16_batch = LDS_L16_BATCH;
+#ifdef PYGIM_LDS_ABLATE
+    in.ablate_build = true;
+#endif
+    const LdsLaunch L = lds_plan_launch(in, lds_launch_knobs());
+    if (L.refusal) return fail(PYGIM_ERR_INVALID, L.refusal);
+    const LdsKernelFn fn = lds_kernel_fn(L.kernel);
+    if (!fn) return fail(PYGIM_ERR_INVALID, "internal: no LDS-staged kernel for this plan");
     KernelTimer kt(g, st, !p.is_extra || p.timed);
+    // 2. the staged copy of X, and the scratch block of partial and parked sums: ONE allocation, made before anything is launched into it
     XsPin pin;
-    void *xs_use = const_cast<void *>(lds_xs);
-    // A product of ONE slice whose rows of X are exactly the staged row (64 FLT32 / INT32 features at a stride of 64; 128 INT16; 64 of an 8-byte type) needs no copy:
-    // the caller's matrix IS the slice-major form.  The last chunk's rows beyond the matrix are read too (never used): they must lie inside the caller's allocation.
-    // (All rows x 64 FLT32 features: 0.61 -> 0.59 ms.)
-    if (!xs_use && g_tune.lds_direct_x && nslices == 1 && !HS && !WIDE8 && !p.lds_col_order && (size_t)ldx * sizeof(T) == ROWB && (size_t)w * sizeof(T) == ROWB &&
-        ((uintptr_t)X & 255) == 0) {
-        void *base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)X) == hipSuccess && base && (const char *)X + (size_t)rows_pad * ROWB <= (const char *)base + size)
-            xs_use = const_cast<void *>((const void *)X);
-        else
-            (void)hipGetLastError();
-    }
-    if (!xs_use) {
-        std::lock_guard<std::mutex> lk(g_ctx.mu);
-        if (g->x_unchanged) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            Context::XsBuf *hit = nullptr;
-            for (auto &kv : g_ctx.xs_bufs) {
-                Context::XsBuf &b = kv.second;
-                // (the padded row count depends on the part's chunk size: a copy made for another ring geometry has another slice stride)
-                if (kv.first.first == dev && b.ptr && b.src == (const void *)X && b.ld == ldx && b.rows == p.ncols && b.w == (int64_t)w &&
-                    b.es == sizeof(T) && b.kind == (HS ? 5 : WIDE8 ? 3 : 1) && b.rows_pad == rows_pad && b.order == (const void *)p.lds_col_order && b.bytes >= need &&
-                    (!hit || b.stamp > hit->stamp))
-                    hit = &b;
-            }
-            if (hit) {
-                hit->stamp = ++g_ctx.xs_clock;
-                hit->in_use++;
-                xs_use = hit->ptr;
-                pin.hold(xs_use);
-            }
-        }
-        if (!xs_use) {
-            Context::XsBuf *b = nullptr;
-            if (int rc = xs_buffer_locked(st, std::max<size_t>(need, 256), &b)) return rc;
-            xs_use = b->ptr;
-            pin.hold(xs_use);
-            b->src = X;
-            b->ld = ldx;
-            b->rows = p.ncols;
-            b->w = (int64_t)w;
-            b->es = sizeof(T);
-            b->kind = HS ? 5 : WIDE8 ? 3 : 1;
-            b->rows_pad = rows_pad;
-            b->order = p.lds_col_order;
-            const uint64_t threads = (uint64_t)p.ncols * nslices * 16;
-            if (HS) {
-                if constexpr (sizeof(T) == 4) {
-                    const uint64_t th = rows_pad * 16;
-                    hipLaunchKernelGGL((k_slice_pack_hs<T>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st, X, ldx, (uint32_t)p.ncols, w, (uint32_t)rows_pad, (T *)xs_use);
-                }
-            } else if constexpr (WIDE8) {
-                if (threads > 0)
-                    hipLaunchKernelGGL(k_slice_pack_widen8, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const int8_t *)X, ldx,
-                                       (uint32_t)p.ncols, w, nslices, (int16_t *)xs_use, (uint32_t)rows_pad, (const uint32_t *)p.lds_col_order);
-            } else if constexpr (EL8) {
-                const uint64_t th8 = (uint64_t)p.ncols * nslices * 32;   // 32 pieces of 16 bytes per 512-byte row
-                if (th8 > 0)
-                    hipLaunchKernelGGL((k_slice_pack<T, 2, 5>), dim3((unsigned)((th8 + 255) / 256)), dim3(256), 0, st, X, ldx,
-                                       (uint32_t)p.ncols, w, nslices, (T *)xs_use, (uint32_t)rows_pad, (const uint32_t *)p.lds_col_order);
-            } else if (threads > 0) {
-                hipLaunchKernelGGL((k_slice_pack<T, PVEC, 4>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, X, ldx,
-                                   (uint32_t)p.ncols, w, nslices, (T *)xs_use, (uint32_t)rows_pad, (const uint32_t *)p.lds_col_order);
-            }
-        }
-    }
+    const void *xs = lds_xs;
+    if (!xs)
+        if (int rc = lds_stage_x<T>(g, p, L.xs, L.x_in_place, X, ldx, w, st, pin, &xs)) return rc;
+    if (L.scratch_bytes)
+        if (int rc = ensure(&g->scratch, &g->scratch_bytes, L.scratch_bytes)) return rc;   // (grows before the first product only)
+    // 3. the arguments
+    const uint32_t *kernel_amax = L.kernel_amax ? deq_amax : nullptr;
     LdsArgs a{};
-    a.tok = p.lds_tok;
-    a.tiles = p.lds_tiles;
-    a.rowmap = p.lds_rowmap;
-    a.xs = (const char *)xs_use;
-    a.c = (char *)C;
-    a.slice_stride = rows_pad * ROWB;
-    a.ldc_bytes = (uint32_t)((size_t)ldc * (((WIDE8 || sizeof(T) == 2) && deq_amax) ? 4 : sizeof(T)));   // (the dequantising store writes floats)
-    a.w = w_lanes;
-    a.nslices = nslices;
-    a.ntiles = p.lds_ntiles;
-    a.accumulate = accumulate ? 1 : 0;
-    // column-split plans: the tiles write the partial sums of column range c to row r + c * nrows of a scratch block (compact rows of
-    // w_lanes dwords); k_lds_reduce adds the S blocks in range order into C afterwards
-    const uint32_t S = p.lds_col_splits;
-    const uint64_t ldp = split16 ? (uint64_t)w_lanes * 2 : (uint64_t)w_lanes * 4 / sizeof(T);   // elements of a partial row (split16: 16-bit numbers)
-    const size_t part_es = split16 ? 2 : sizeof(T);
-    const uint64_t lds_rows = p.lds_rows ? p.lds_rows : (uint64_t)p.nrows;   // rows the plan's tiles cover (the rest: k_lds_tail, below)
-    // round 6: the dequantising product on a column-split plan -- the plain kernel writes the ranges' partial sums, k_lds_reduce_deq dequantises where they meet
-    const bool deq_at_reduce = S > 1 && deq_amax != nullptr;
-    if (S > 1) {
-        // (+ what the tail kernels park behind the ranges' partial sums: ONE allocation, made before anything is launched into it)
-        const size_t need = (((size_t)S * (size_t)lds_rows * ldp * part_es + 255) & ~(size_t)255) + (size_t)p.lds_tail_nseg * nslices * 64 * 8;
-        if (int rc = ensure(&g->scratch, &g->scratch_bytes, std::max<size_t>(need, 256))) return rc;
-        a.c = (char *)g->scratch;
-        a.ldc_bytes = (uint32_t)(ldp * part_es);
-        a.accumulate = 0;
-    }
-    const uint32_t *kernel_amax = (deq_at_reduce || split16) ? nullptr : deq_amax;
-    a.wdelta = p.lds_wdelta;
-    a.deq_amax = kernel_amax;
-    a.deq_log2 = deq_log2;
+    a.tok = p.lds_tok; a.tiles = p.lds_tiles; a.rowmap = p.lds_rowmap; a.xs = (const char *)xs; a.c = L.to_scratch ? (char *)g->scratch : (char *)C;
+    a.slice_stride = L.xs.slice_stride; a.ldc_bytes = L.ldc_bytes; a.w = L.w_lanes; a.nslices = L.xs.nslices; a.ntiles = L.ntiles; a.accumulate = L.accumulate;
+    a.wdelta = p.lds_wdelta; a.deq_amax = kernel_amax; a.deq_log2 = deq_log2;
     a.post_mul = kernel_amax ? g->post_mul : nullptr;   // (the per-column epilogue rides the dequantising store only)
     a.post_add = kernel_amax ? g->post_add : nullptr;
     a.post_relu = kernel_amax ? g->post_relu : 0;
-    const LdsXcdLayout lay = lds_xcd_layout(p, nslices, EL8);
-    a.xcd_group = lay.group;
-    a.xcd_sx = lay.sx;
-    a.touch_share = lay.touch_share;
-    a.half_split = HS ? 1u : 0u;
-    a.xcd_contig = (a.xcd_group && p.lds_contig_tiles) ? (p.lds_ntiles + a.xcd_group - 1) / a.xcd_group : 0;
-    const uint32_t grid = a.xcd_group ? 8 * ((p.lds_ntiles + a.xcd_group - 1) / a.xcd_group) * a.xcd_sx : p.lds_ntiles * nslices;
-    using KernelFn = void (*)(LdsArgs);
-    KernelFn fn = nullptr;
-    const bool long16 = p.lds_nw == 16 && p.lds_batch == LDS_L16_BATCH;   // the 16-token-batch geometry (no values)
-    if (p.lds_is_code) {   // the schedule compiled into machine code: 16 waves x 96 accumulators, or 8 x 228 (k_lds_code8_*)
-        if (!g_tune.lds_code || g_tune.lds_ablate) return fail(PYGIM_ERR_INVALID, "this group's LDS plan is a code stream: lds_code was switched off (or lds_ablate on) after it was created");
-        const bool w8 = p.lds_nw == 8;
-        if constexpr (EL8) {
-            if (!w8 || kernel_amax || S > 1 || p.lds_row_bytes != 512) return fail(PYGIM_ERR_INVALID, "internal: 8-byte LDS-staged product on an unsupported plan");
-            if constexpr (std::is_same<T, double>::value) fn = k_lds_code8_f64;
-            else fn = k_lds_code8_i64;
-        } else if constexpr (sizeof(T) == 1) {
-            if (!w8 || (accumulate && S <= 1)) return fail(PYGIM_ERR_INVALID, "internal: INT8 LDS-staged product on an unsupported plan");
-            fn = split16 ? k_lds_code8_i16 : kernel_amax ? k_lds_code8_i8_deq : k_lds_code8_i8;   // (widened to 16 bits in the staged copy: the INT16 stream)
-        } else if constexpr (sizeof(T) == 2) {
-            if ((kernel_amax || split16) && !w8) return fail(PYGIM_ERR_INVALID, "internal: dequantising LDS-staged product on an unsupported plan");
-            fn = kernel_amax ? k_lds_code8_i16_deq : (w8 ? k_lds_code8_i16 : k_lds_code_i16);   // (two features to a lane: v_pk_add_u16)
-        } else if constexpr (std::is_same<T, float>::value) {
-            fn = kernel_amax ? (w8 ? k_lds_code8_f32_deq : k_lds_code_f32_deq) : (w8 ? k_lds_code8_f32 : k_lds_code_f32);
-        } else {
-            fn = kernel_amax ? (w8 ? k_lds_code8_i32_deq : k_lds_code_i32_deq) : (w8 ? k_lds_code8_i32 : k_lds_code_i32);
-        }
-        // measurement build (scripts/exp_stamps.py): the caller's buffer gets four clock stamps per wave of every workgroup
-        if (g_tune.lds_stamp && fn == k_lds_code8_f32) {
-            fn = k_lds_code8_f32_ts;
-            a.stamps = (uint64_t *)(uintptr_t)g_tune.lds_stamp;
-        }
-        a.code = p.lds_code;
-        a.code_start = p.lds_code_start;
-        a.piece_bytes = p.lds_code_piece;
-    } else if constexpr (sizeof(T) == 1 || sizeof(T) == 8) {
-        return fail(PYGIM_ERR_INVALID, "internal: the INT8 / INT64 / DBL64 LDS-staged product exists in the code-stream form only");
-    } else if (kernel_amax) {
-        if (p.lds_nw != 16 || p.lds_wdelta || sizeof(T) != 4) return fail(PYGIM_ERR_INVALID, "internal: dequantising LDS-staged product on an unsupported plan");
-        if constexpr (std::is_same<T, float>::value) fn = long16 ? k_lds_spmm_f32_w16b_deq : k_lds_spmm_f32_w16_deq;
-        else if constexpr (std::is_same<T, int32_t>::value) fn = long16 ? k_lds_spmm_i32_w16b_deq : k_lds_spmm_i32_w16_deq;
-    } else if constexpr (sizeof(T) == 2) {
-        if (p.lds_nw != 16) return fail(PYGIM_ERR_INVALID, "internal: INT16 LDS-staged product needs the 16-wave plan");
-        fn = long16 ? k_lds_spmm_i16_w16b : (p.lds_wdelta ? k_lds_spmm_i16_w16_val : k_lds_spmm_i16_w16);
-    } else if (long16) {
-        if constexpr (std::is_same<T, float>::value) fn = k_lds_spmm_f32_w16b;
-        else fn = k_lds_spmm_i32_w16b;
-    } else if constexpr (std::is_same<T, float>::value) {
-        fn = p.lds_nw == 16 ? (p.lds_wdelta ? k_lds_spmm_f32_w16_val : k_lds_spmm_f32_w16) : k_lds_spmm_f32_w8;
-#ifdef PYGIM_LDS_ABLATE
-        if (p.lds_nw == 16 && !p.lds_wdelta && !long16) {  // timing experiments (wrong results, scripts/gen_lds_kernel.py; make ablate)
-            switch (g_tune.lds_ablate) {
-                case 6: fn = k_lds_spmm_f32_w16_ab6; break;
-                case 7: fn = k_lds_spmm_f32_w16_ab7; break;
-                case 10: fn = k_lds_spmm_f32_w16_ab10; break;
-                case 11: fn = k_lds_spmm_f32_w16_ab11; break;
-                case 12: fn = k_lds_spmm_f32_w16_ab12; break;
-                case 15: fn = k_lds_spmm_f32_w16_ab15; break;
-                case 16: fn = k_lds_spmm_f32_w16_ab16; break;
-                case 17: fn = k_lds_spmm_f32_w16_ab17; break;
-                case 18: fn = k_lds_spmm_f32_w16_ab18; break;
-                case 19: fn = k_lds_spmm_f32_w16_ab19; break;
-                default: break;
-            }
-        }
-#else
-        if (g_tune.lds_ablate) return fail(PYGIM_ERR_INVALID, "lds_ablate needs the ablation build (make -C pygim_amd/csrc ablate)");
-#endif
-    } else {
-        fn = p.lds_nw == 16 ? (p.lds_wdelta ? k_lds_spmm_i32_w16_val : k_lds_spmm_i32_w16) : k_lds_spmm_i32_w8;
+    a.xcd_group = L.xcd_group; a.xcd_sx = L.xcd_sx; a.touch_share = L.touch_share; a.half_split = L.half_split; a.xcd_contig = L.xcd_contig;
+    if (p.lds_is_code) {
+        a.code = p.lds_code; a.code_start = p.lds_code_start; a.piece_bytes = p.lds_code_piece;
     }
-    if (kernel_amax && g_tune.lds_ablate) return fail(PYGIM_ERR_INVALID, "lds_ablate is a timing experiment of the plain kernel");
-    if (!fn) return fail(PYGIM_ERR_INVALID, "internal: no LDS-staged kernel for this plan");
+    if (L.kernel.stamp) a.stamps = (uint64_t *)(uintptr_t)g_tune.lds_stamp;   // measurement build (scripts/exp_stamps.py)
+    // 4. the dynamic-LDS attribute, once per device and kernel
     {
-        static std::set<std::pair<int, KernelFn>> attr_done;   // (the attribute is per device)
+        static std::set<std::pair<int, LdsKernelFn>> attr_done;
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
         std::lock_guard<std::mutex> lk(g_ctx.mu);
@@ -533,88 +463,58 @@ int launch_lds(Group *g, Part &p, const T *X, int64_t ldx, T *C, int64_t ldc, ui
             attr_done.insert({dev, fn});
         }
     }
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(p.lds_nw * 64), LDS_BYTES, st, a);
+    // 5. the launch, then the reduce of a column-split plan's partial sums, then the rows the plan leaves to the tail kernels
+    hipLaunchKernelGGL(fn, dim3(L.grid), dim3(L.block), LDS_BYTES, st, a);
     g->lds_runs++;
-    if (split16 && lds_rows > 0 && w > 0) {
-        const uint64_t total = lds_rows * w;
-        const dim3 rg((unsigned)((total + 255) / 256));
-        if (!deq_amax)
-            hipLaunchKernelGGL((k_lds_reduce16<0>), rg, dim3(256), 0, st, (const int16_t *)g->scratch, S, lds_rows, w, ldp, (void *)C, ldc, accumulate ? 1 : 0, nullptr, 0, nullptr, nullptr, 0);
-        else if (WIDE8)
-            hipLaunchKernelGGL((k_lds_reduce16<1>), rg, dim3(256), 0, st, (const int16_t *)g->scratch, S, lds_rows, w, ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
-        else
-            hipLaunchKernelGGL((k_lds_reduce16<2>), rg, dim3(256), 0, st, (const int16_t *)g->scratch, S, lds_rows, w, ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
-    } else if (S > 1 && lds_rows > 0 && w > 0 && sizeof(T) == 4 && (w & 3) == 0 && (ldp & 3) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0) {
-        // four features to a thread (16-byte loads and stores): a 1/8 row share's reduce 32 -> 21 us
-        if constexpr (sizeof(T) == 4) {
-            const uint64_t total4 = lds_rows * (w >> 2);
-            const dim3 rg((unsigned)((total4 + 255) / 256));
-            if (deq_at_reduce)
-                hipLaunchKernelGGL((k_lds_reduce_v4<T, true>), rg, dim3(256), 0, st, (const T *)g->scratch, S, lds_rows, w, ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul,
-                                   g->post_add, g->post_relu);
-            else
-                hipLaunchKernelGGL((k_lds_reduce_v4<T, false>), rg, dim3(256), 0, st, (const T *)g->scratch, S, lds_rows, w, ldp, (void *)C, ldc, accumulate ? 1 : 0, nullptr, 0, nullptr,
-                                   nullptr, 0);
-        }
-    } else if (S > 1 && lds_rows > 0 && w > 0) {
-        const uint64_t total = lds_rows * w;
-        if constexpr (sizeof(T) == 4) {
-            if (deq_at_reduce)
-                hipLaunchKernelGGL((k_lds_reduce_deq<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T *)g->scratch, S, lds_rows, w, ldp, (float *)C, ldc,
-                                   deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
-        }
-        if (!deq_at_reduce)
-            hipLaunchKernelGGL((k_lds_reduce<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T *)g->scratch, S, lds_rows, w, ldp, C,
-                               ldc, accumulate ? 1 : 0);
+    const dim3 rg((unsigned)((L.reduce_total + 255) / 256));
+    const uint32_t S = L.col_splits;
+    const int acc = accumulate ? 1 : 0;
+    const int16_t *s16 = (const int16_t *)g->scratch;
+    const T *sT = (const T *)g->scratch;
+    switch (L.reduce) {
+        case LDS_RED_16_PLAIN:
+            hipLaunchKernelGGL((k_lds_reduce16<0>), rg, dim3(256), 0, st, s16, S, L.lds_rows, w, L.ldp, (void *)C, ldc, acc, nullptr, 0, nullptr, nullptr, 0);
+            break;
+        case LDS_RED_16_DEQ8:
+            hipLaunchKernelGGL((k_lds_reduce16<1>), rg, dim3(256), 0, st, s16, S, L.lds_rows, w, L.ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
+            break;
+        case LDS_RED_16_DEQ16:
+            hipLaunchKernelGGL((k_lds_reduce16<2>), rg, dim3(256), 0, st, s16, S, L.lds_rows, w, L.ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
+            break;
+        case LDS_RED_V4:
+            if constexpr (sizeof(T) == 4) {
+                if (L.deq_at_reduce)
+                    hipLaunchKernelGGL((k_lds_reduce_v4<T, true>), rg, dim3(256), 0, st, sT, S, L.lds_rows, w, L.ldp, (void *)C, ldc, 0, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
+                else
+                    hipLaunchKernelGGL((k_lds_reduce_v4<T, false>), rg, dim3(256), 0, st, sT, S, L.lds_rows, w, L.ldp, (void *)C, ldc, acc, nullptr, 0, nullptr, nullptr, 0);
+            }
+            break;
+        case LDS_RED_DEQ:
+            if constexpr (sizeof(T) == 4)
+                hipLaunchKernelGGL((k_lds_reduce_deq<T>), rg, dim3(256), 0, st, sT, S, L.lds_rows, w, L.ldp, (float *)C, ldc, deq_amax, deq_log2, g->post_mul, g->post_add, g->post_relu);
+            break;
+        case LDS_RED_PLAIN: hipLaunchKernelGGL((k_lds_reduce<T>), rg, dim3(256), 0, st, sT, S, L.lds_rows, w, L.ldp, C, ldc, acc); break;
+        default: break;
     }
-    if (lds_rows < (uint64_t)p.nrows && w > 0) {   // the share's last rows, from the same staged copy (k_lds_tail_seg / _fin)
-        if constexpr (sizeof(T) == 4) {
+    if constexpr (sizeof(T) == 4) {
+        if (L.tail) {   // the share's last rows, from the same staged copy (k_lds_tail_seg / _fin)
             using A = typename AccOf<T>::type;
-            if (!p.lds_tail_segs || !p.lds_tail_rowseg) return fail(PYGIM_ERR_INVALID, "internal: an LDS plan that leaves rows out has no segment table for them");
-            const uint32_t ntail = (uint32_t)((uint64_t)p.nrows - lds_rows);
-            const size_t split_bytes = S > 1 ? (((size_t)S * (size_t)lds_rows * ldp * sizeof(T) + 255) & ~(size_t)255) : 0;
-            const size_t park_bytes = (size_t)p.lds_tail_nseg * nslices * 64 * sizeof(A);
-            if (int rc = ensure(&g->scratch, &g->scratch_bytes, std::max<size_t>(split_bytes + park_bytes, 256))) return rc;   // (grows before the first product only)
-            A *parked = (A *)((char *)g->scratch + split_bytes);
+            A *parked = (A *)((char *)g->scratch + L.split_bytes);
+            const dim3 fin(L.ntail, L.xs.nslices);
             if (p.lds_tail_nseg > 0)   // (rows without entries have no segment: k_lds_tail_fin still writes their zeros)
-                hipLaunchKernelGGL((k_lds_tail_seg<T>), dim3(p.lds_tail_nseg, nslices), dim3(512), 0, st, p.lds_tail_segs, p.lds_tail_nseg, p.colind, (const char *)xs_use,
-                                   (uint64_t)(rows_pad * ROWB), parked);
-            const int64_t ldc_b = (int64_t)ldc * 4;
+                hipLaunchKernelGGL((k_lds_tail_seg<T>), dim3(p.lds_tail_nseg, L.xs.nslices), dim3(512), 0, st, p.lds_tail_segs, p.lds_tail_nseg, p.colind, (const char *)xs,
+                                   L.xs.slice_stride, parked);
             if (deq_amax)
-                hipLaunchKernelGGL((k_lds_tail_fin<T, true>), dim3(ntail, nslices), dim3(64), 0, st, p.lds_tail_rowseg, (uint32_t)lds_rows, parked, w, (void *)C, ldc_b, 0, deq_amax,
-                                   deq_log2, g->post_mul, g->post_add, g->post_relu);
+                hipLaunchKernelGGL((k_lds_tail_fin<T, true>), fin, dim3(64), 0, st, p.lds_tail_rowseg, (uint32_t)L.lds_rows, parked, w, (void *)C, L.tail_ldc_bytes, 0, deq_amax, deq_log2,
+                                   g->post_mul, g->post_add, g->post_relu);
             else
-                hipLaunchKernelGGL((k_lds_tail_fin<T, false>), dim3(ntail, nslices), dim3(64), 0, st, p.lds_tail_rowseg, (uint32_t)lds_rows, parked, w, (void *)C, ldc_b,
-                                   accumulate ? 1 : 0, nullptr, 0, nullptr, nullptr, 0);
-        } else {
-            return fail(PYGIM_ERR_INVALID, "internal: an LDS plan that leaves rows to the tail kernels exists for 4-byte element types only");
+                hipLaunchKernelGGL((k_lds_tail_fin<T, false>), fin, dim3(64), 0, st, p.lds_tail_rowseg, (uint32_t)L.lds_rows, parked, w, (void *)C, L.tail_ldc_bytes, acc, nullptr, 0,
+                                   nullptr, nullptr, 0);
         }
     }
     kt.stop();
     HIP_TRY(hipGetLastError());
     return 0;
-}
-
-template <typename T> bool want_lds(const Group *g, const Part &p, uint32_t w, int64_t ldc, const void *C, bool accumulate = false) {
-    if constexpr (sizeof(T) == 8) {  // INT64 / DBL64: the 8-wave code stream on 512-byte rows (unit weights)
-        if (!p.lds_is_code || p.lds_nw != 8 || p.lds_row_bytes != 512 || p.lds_col_splits > 1 || false) return false;   // (valued DBL64 / INT64: round 5 -- a valued part has a code plan only when its values allow it)
-    } else if (p.lds_row_bytes == 512) return false;
-    if constexpr (sizeof(T) == 1) {  // INT8 rides the 8-wave INT16 code stream (features widened to 16 bits in the staged copy); it neither accumulates
-                                     // into C nor splits tiles into column ranges
-        if (!p.lds_is_code || p.lds_nw != 8 || (accumulate && p.lds_col_splits <= 1)) return false;   // (round 5: valued too -- the values are part of the stream; round 6: column-split
-                                                                                                     // plans -- k_lds_reduce16 makes the bytes, and adds into C when asked)
-        if ((int64_t)(w / 2) < g_tune.lds_min_width) return false;
-    }
-    if constexpr (sizeof(T) == 2) {  // two features to a lane: whole lanes, dword-aligned rows of C, the 16-wave plan
-        if ((w & 1) || (ldc & 1) || ((uintptr_t)C & 3) || (p.lds_nw != 16 && !p.lds_is_code)) return false;
-    }
-    if (!p.lds_tiles || g_tune.lds_mode == 2 || (!p.lds_is_code && (p.vals != nullptr) != (p.lds_wdelta != 0)) || g->deq_out || g->pre_xs) return false;
-    if (p.lds_half && (sizeof(T) != 4 || w > 32)) return false;   // (a half-split plan: plain products of at most 32 lanes)
-    if (p.lds_is_code && (!g_tune.lds_code || g_tune.lds_ablate)) return false;   // (a code-stream plan serves no token kernel: the sweep instead)
-    if (g_tune.lds_mode == 0 && (g_tune.panel_mode == 1 || g_tune.csr_kernel != 0 || g_tune.force_vec_bytes != 0)) return false;  // another kernel was asked for by name
-    if (sizeof(T) > 1 && (int64_t)(sizeof(T) == 8 ? (size_t)w : (size_t)w * sizeof(T) / 4) < (sizeof(T) == 8 ? g_tune.lds_min_width8 : g_tune.lds_min_width)) return false;   // (lanes: 4-byte units of a row; 8-byte: features)
-    if ((uint64_t)ldc * sizeof(T) >= (1ull << 32)) return false;
-    return true;
 }
 
 template <typename T>
@@ -623,7 +523,7 @@ int launch_block(Group *g, Part &p, const void *X, int64_t ldx, void *C, int64_t
     const T *x = (const T *)X;
     T *c = (T *)C;
     const uint32_t ww = (uint32_t)w;
-    if (want_lds<T>(g, p, ww, ldc, C, accumulate)) return launch_lds<T>(g, p, x, ldx, c, ldc, ww, accumulate, st);
+    if (lds_takes(g, p, ww, ldc, C, accumulate)) return launch_lds<T>(g, p, x, ldx, c, ldc, ww, accumulate, st);
     // SpMV end of the path: rows of X of at most 4 elements -> lanes over the ENTRIES of a row (k_csr_vec)
     if (ww <= 4 && g_tune.vec_kernel && g_tune.force_vec_bytes == 0 && g_tune.csr_kernel == 0 && p.rowptr && p.nrows > 0) {
         // LDS-staged form: the plan's column panels with 16-bit local ids, a panel of X (panel_cols x w elements) plus the
@@ -788,28 +688,13 @@ int launch_block_main(Group *g, Part &p, const void *X, int64_t ldx, void *C, in
                       hipStream_t st);
 
 static bool hybrid_takes(const Group *g, const Part &d, uint32_t w, int64_t ldc, const void *C) {
-    switch (g->dtype) {
-        case PYGIM_INT8: return want_lds<int8_t>(g, d, w, ldc, C, false);
-        case PYGIM_INT16: return want_lds<int16_t>(g, d, w, ldc, C, false);
-        case PYGIM_INT32: return want_lds<int32_t>(g, d, w, ldc, C, false);
-        case PYGIM_FLT32: return want_lds<float>(g, d, w, ldc, C, false);
-        default: return false;
-    }
+    return g->dtype != PYGIM_INT64 && g->dtype != PYGIM_DBL64 && lds_takes(g, d, w, ldc, C);   // (the density split serves the 1-, 2- and 4-byte types)
 }
 
 // true when launch_block_any(g, p, ..., C, ldc, w, accumulate = false) is ONE pass of the LDS-staged product that writes every element of C exactly once and
 // reads none (no correction part, no density split adding on top): the call whose C may be the caller's page-locked host tensor (run_group_windows)
 static bool lds_writes_c_once(const Group *g, const Part &p, uint32_t w, int64_t ldc, const void *C) {
-    if (p.extra || p.hy_dense || p.hy_sparse || w == 0 || p.nrows == 0) return false;
-    switch (g->dtype) {
-        case PYGIM_INT8: return want_lds<int8_t>(g, p, w, ldc, C, false);
-        case PYGIM_INT16: return want_lds<int16_t>(g, p, w, ldc, C, false);
-        case PYGIM_INT32: return want_lds<int32_t>(g, p, w, ldc, C, false);
-        case PYGIM_INT64: return want_lds<int64_t>(g, p, w, ldc, C, false);
-        case PYGIM_FLT32: return want_lds<float>(g, p, w, ldc, C, false);
-        case PYGIM_DBL64: return want_lds<double>(g, p, w, ldc, C, false);
-    }
-    return false;
+    return !(p.extra || p.hy_dense || p.hy_sparse || w == 0 || p.nrows == 0) && lds_takes(g, p, w, ldc, C);
 }
 
 int launch_block_any(Group *g, Part &p, const void *X, int64_t ldx, void *C, int64_t ldc, int64_t w,

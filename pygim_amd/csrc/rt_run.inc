@@ -666,6 +666,8 @@ static Part *fusable_part(Group *g) {
 
 // the part whose LDS-staged plan can carry the conv layers' quantised aggregation with the dequantisation in its store
 // (INT32 / FLT32 adjacency types; the per-column epilogue, if any, is applied in the same store)
+// Its conditions on the plan and the tunables are RESTATED in tests/native/lds_launch_main.cpp (fusable_rest), where a sweep checks that what this gate
+// accepts lds_plan_launch launches: change the two together.
 template <typename T>
 static Part *lds_fusable_part(Group *g) {
     if constexpr (!(std::is_same<T, float>::value || std::is_same<T, int32_t>::value || std::is_same<T, int8_t>::value || std::is_same<T, int16_t>::value)) return nullptr;
@@ -707,14 +709,14 @@ static int quant_run_t(Group *g, const float *X, int64_t ldx, float *out, float 
             // store dequantises (no quantised matrix, no integer result).  INT8 (the conv layers' own type, models/quantize.py:22-23):
             // the quantised values are staged as 16-bit numbers, 128 features to a slice, and summed by the INT16 stream
             using S = typename std::conditional<sizeof(T) == 1, int16_t, T>::type;
-            constexpr uint32_t EPS = 256 / sizeof(S);
-            const uint32_t nslices = (h + EPS - 1) / EPS;
-            const uint64_t rows_pad = lds_rows_pad((uint64_t)p->ncols, p->lds_kc);
+            const LdsStaged sg = lds_staged(sizeof(T), sizeof(T) == 1, h, (uint64_t)p->ncols, p->lds_kc, p->lds_half);   // (the copy launch_lds will read)
+            const uint32_t nslices = sg.nslices;
+            const uint64_t rows_pad = sg.rows_pad;
             void *xs = nullptr;
             {
                 std::lock_guard<std::mutex> lk(g_ctx.mu);
                 Context::XsBuf *b = nullptr;
-                if (int rc = xs_buffer_locked(st, std::max<size_t>((size_t)rows_pad * nslices * 256, 256), &b)) return rc;
+                if (int rc = xs_buffer_locked(st, std::max<size_t>(sg.bytes, 256), &b)) return rc;
                 b->src = nullptr;  // quantised values of a float matrix: never matched by x_unchanged
                 xs = b->ptr;
             }

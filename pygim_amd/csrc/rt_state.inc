@@ -259,15 +259,20 @@ struct Context {
     // slice-major copies of X for the panel sweep: one buffer per (device, launch stream) -- products on different
     // streams never share a buffer -- each with a record of what it holds, for callers that pass x_unchanged.
     // At most XS_MAX buffers are kept (least recently used goes first); all are freed with the last group.
-    struct XsBuf {
-        void *ptr = nullptr;
-        size_t bytes = 0;
-        const void *src = nullptr;  // what the buffer holds: X pointer, stride, rows, width, element size
+    struct XsKey {   // what a buffer holds (the LDS-staged product compares and records it as a whole, lds_stage_x)
+        const void *src = nullptr;  // X pointer, stride, rows, width, element size
         int64_t ld = 0, rows = 0, w = 0;
         const void *order = nullptr;   // the copy's rows are X[order[pos]] (a density-split part), or X's own order
-        uint64_t rows_pad = 0;  // kind 1 / 3: rows of a slice in THIS copy (whole chunks of the part that packed it) -> its slice stride
+        uint64_t rows_pad = 0;  // kind 1 / 3 / 5: rows of a slice in THIS copy (whole chunks of the part that packed it) -> its slice stride
         size_t es = 0;
-        int kind = 0;  // 0 = 128-byte slices (sweep), 1 = 256-byte slices, rows padded to whole chunks (LDS-staged product)
+        int kind = 0;  // 0 = 128-byte slices (sweep), 1 = 256-byte slices, rows padded to whole chunks (LDS-staged product; 3: INT8 widened, 5: half-split)
+        bool operator==(const XsKey &o) const {
+            return src == o.src && ld == o.ld && rows == o.rows && w == o.w && order == o.order && rows_pad == o.rows_pad && es == o.es && kind == o.kind;
+        }
+    };
+    struct XsBuf : XsKey {
+        void *ptr = nullptr;
+        size_t bytes = 0;
         uint64_t stamp = 0;
         int in_use = 0;  // handed to a call that has not enqueued its kernels yet: not an eviction victim
     };
