@@ -179,7 +179,21 @@ int pygim_group_create_transposed(int format, int dtype, int n_parts,
  *
  * stream: a hipStream_t (NULL = the default stream).  With device pointers the
  * call only enqueues work; with host pointers it returns after the result has
- * been copied back.                                                           */
+ * been copied back.
+ *
+ * Non-finite operands (FLT32 / DBL64; every form of the product -- row per wave,
+ * long-row segments, native COO, the SpMV end, the panel sweep, the LDS-staged
+ * forms, the density split, merged and unmerged parts, host windows, the
+ * transposed group -- is held to this by tests/test_group_nonfinite_gpu.py):
+ *   - a NaN or infinite feature or value reaches exactly the outputs the CPU
+ *     loop (oracle/spmm_oracle.c) gives it to: NaN where that loop has NaN, the
+ *     loop's bits everywhere else -- lanes, tokens and slots that do no work add
+ *     nothing, whatever X holds in the column they point at;
+ *   - a stored 0 times an infinity is NaN;
+ *   - no explicit zero is dropped, at creation or in a kernel;
+ *   - a product never returns -0.0: every sum starts from +0.
+ * (Finite sums that mix magnitudes round by the order a form adds them in; that
+ * is each form's tolerance, stated with it, and not part of this contract.)   */
 int pygim_spmm_run_group(int64_t handle, const void *const *B_parts, void *out, void *stream);
 /* the same with x_unchanged (see "Threading" above): 1 = B_parts hold exactly what the most
  * recent product on the same pointers held, its slice-major copy may be reused.   */
