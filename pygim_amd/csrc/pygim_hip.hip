@@ -23,6 +23,7 @@
 #include "lds_hybrid_dev.hpp"
 #include "lds_form.hpp"
 #include "lds_launch.hpp"
+#include "run_plan.hpp"
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
 #include "row_gather_dev.hpp"
@@ -1365,14 +1366,11 @@ int pygim_spmv_run_group(int64_t handle, const void *const *B_vectors, void *out
         for (auto wdt : p.dense_cols)
             if (wdt != 1) return fail(PYGIM_ERR_INVALID, "spmv group: every dense part must be one column wide");
     }
-    if (!B_vectors || !out) return fail(PYGIM_ERR_INVALID, "null vectors or output");
-    for (size_t j = 0; j < nvec; j++)
-        if (!B_vectors[j]) return fail(PYGIM_ERR_INVALID, "null vector");
-    const bool dev_in = is_device_ptr(B_vectors[0]);
-    const bool dev_out = is_device_ptr(out);
-    for (size_t j = 1; j < nvec; j++)
-        if (is_device_ptr(B_vectors[j]) != dev_in) return fail(PYGIM_ERR_INVALID, "vectors mix host and device memory");
-    if (dev_in != dev_out) return fail(PYGIM_ERR_INVALID, "vectors and output must both be host or both be device memory");
+    static const OperandTexts texts{"null vectors or output", "null vector", "vectors mix host and device memory",
+                                    "vectors and output must both be host or both be device memory"};
+    bool dev_in = false;
+    if (int rc = check_dense_operands(B_vectors, nvec, out, texts, &dev_in)) return rc;
+    const bool dev_out = dev_in;   // (checked: both on one side)
     const uint64_t n = (uint64_t)g->total_cols;
     // layout of stage_in: [packed panel n x nvec][raw vectors (host mode only)]
     const size_t panel_bytes = ((size_t)n * nvec * es + 255) & ~(size_t)255;

@@ -1,5 +1,5 @@
 // rt_run.inc -- part of pygim_hip.hip (file scope): group assembly helpers (pattern + correction split, narrow values, merged parts), the shared body of the
-// run_group entry points, the conv layers' quantiser around the product.
+// run_group entry points (run_group_common: it does what run_plan.hpp planned), the conv layers' quantiser around the product.
 template <typename T>
 static void launch_pack(const void *const *d_ptrs, uint32_t gcount, uint64_t n, void *out, hipStream_t st) {
     const uint64_t total = n * gcount;
@@ -8,11 +8,6 @@ static void launch_pack(const void *const *d_ptrs, uint32_t gcount, uint64_t n, 
                        (const T *const *)d_ptrs, gcount, n, (T *)out);
 }
 
-
-// shared body of the three run_group flavours.
-//   windows[k]   : dense operand k (flattened over parts when per_part)
-//   ld[k]        : its row stride in elements
-//   per_part     : grande layout (each window holds only the rows of its own sparse part)
 // Integer weights that are 1 except for a few entries (at most nnz / 32; nnz / 64 until the density split, which takes patterns only: a products-shaped
 // community graph coalesces to 2 % of weights above 1): keep the unit-weight pattern in `p` and move
 // the exceptions, as (weight - 1), into p.extra (CSR by rows, entries in stored order).  One-time, at group creation.
@@ -210,22 +205,8 @@ int build_merged(Group *g, size_t es, hipStream_t st) {
 // against the engines' 21-38 in the micro-benchmark) was built and lost: 9.0 ms -- its workgroups queue behind the product's, which own every compute unit.
 // The result tensor must be page-locked (the wrappers allocate it so, pim_ops._new_out): a 2-D copy into pageable memory runs at 10 GB/s and blocks the
 // host (12.9 ms), so such a call keeps the serial path.  scripts/micro/pcie_windows.hip, scripts/exp_host_call.py, profiles/r06_pcie_windows.txt.
-struct HostPiece {       // one of the caller's narrow feature blocks inside a window (grande's per-unit windows, ds_parts blocks of a few bytes per row)
-    const char *src;      // host: [rows x pitch_el], contiguous
-    int64_t pitch_el, w;  // its row stride and true width, elements
-    size_t dev_off;       // where the block lands in stage_in (as it is: one 1-D copy)
-    int64_t acol;         // its first column in C (and in the assembled X)
-};
-struct HostWindow {
-    const char *src;      // host
-    int64_t pitch_el;     // host and device row stride of this window's block, elements
-    size_t dev_off;       // byte offset of the window's first element in stage_in
-    int64_t acol, w;      // columns [acol, acol + w) of C
-    // a window ASSEMBLED from several of the caller's blocks: each goes up as it is and is laid into its columns of Group::xcat (row stride xcat_ld elements)
-    // on the device; the product then reads xcat
-    std::vector<HostPiece> pieces;
-    int64_t xcat_ld = 0;
-};
+// WHICH windows a call moves (HostWindow, HostPiece) and whether their products store directly is decided in run_plan.hpp (plan_host_pipeline), without a
+// device; run_group_windows below only moves and multiplies them.
 
 // the caller's page-locked result as the kernels see it (nullptr: pageable memory, or not mapped for this device)
 static char *host_result_on_device(void *out) {
@@ -244,7 +225,7 @@ static int run_group_windows(Group *g, Part &m, const std::vector<HostWindow> &p
     const size_t npw = pw.size();
     // The two copy streams belong to the PROCESS (one pair per device, made at the first pipelined call and kept).  They get the two ends of the priority
     // range: hardware queues are pooled per priority class, so neither shares one with the caller's stream.  (Neither the pair's age nor its priorities
-    // decide how fast the pitched downloads run -- profiles/r06_exp_host_call.txt; see host_direct in run_group_common.)
+    // decide how fast the pitched downloads run -- profiles/r06_exp_host_call.txt; see host_direct in run_plan.hpp plan_host_pipeline.)
     {
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
@@ -279,13 +260,13 @@ static int run_group_windows(Group *g, Part &m, const std::vector<HostWindow> &p
                 for (const HostPiece &pc : q.pieces) {
                     if (xrows <= 0 || pc.w <= 0) continue;
                     char *blk = (char *)g->stage_in + pc.dev_off;
-                    HIP_TRY(hipMemcpyAsync(blk, pc.src, (size_t)xrows * (size_t)pc.pitch_el * es, hipMemcpyHostToDevice, g->pipe_up));
+                    HIP_TRY(hipMemcpyAsync(blk, (const void *)pc.src, (size_t)xrows * (size_t)pc.pitch_el * es, hipMemcpyHostToDevice, g->pipe_up));
                     HIP_TRY(hipMemcpy2DAsync((char *)g->xcat + (size_t)pc.acol * es, (size_t)q.xcat_ld * es, blk, (size_t)pc.pitch_el * es, (size_t)pc.w * es, (size_t)xrows,
                                              hipMemcpyDeviceToDevice, g->pipe_up));
                 }
             } else if (xrows > 0 && wb > 0) {
-                if (wb == pitch) HIP_TRY(hipMemcpyAsync(dx, q.src, wb * (size_t)xrows, hipMemcpyHostToDevice, g->pipe_up));
-                else HIP_TRY(hipMemcpy2DAsync(dx, pitch, q.src, pitch, wb, (size_t)xrows, hipMemcpyHostToDevice, g->pipe_up));
+                if (wb == pitch) HIP_TRY(hipMemcpyAsync(dx, (const void *)q.src, wb * (size_t)xrows, hipMemcpyHostToDevice, g->pipe_up));
+                else HIP_TRY(hipMemcpy2DAsync(dx, pitch, (const void *)q.src, pitch, wb, (size_t)xrows, hipMemcpyHostToDevice, g->pipe_up));
             }
             HIP_TRY(hipEventRecord(g->pipe_ev[2 * k], g->pipe_up));
             HIP_TRY(hipStreamWaitEvent(st, g->pipe_ev[2 * k], 0));
@@ -316,287 +297,140 @@ static int run_group_windows(Group *g, Part &m, const std::vector<HostWindow> &p
     return rc;
 }
 
-static int run_group_common(Group *g, const void *const *windows, const int64_t *ld, bool per_part, void *out,
-                            hipStream_t st) {
-    const size_t es = dtype_size(g->dtype);
-    size_t nwin = 0;
-    if (per_part)
-        for (auto &p : g->parts) nwin += p.dense_cols.size();
-    else
-        nwin = g->parts[0].dense_cols.size();
-    if (!windows || !out) return fail(PYGIM_ERR_INVALID, "null dense operand or output");
-    for (size_t k = 0; k < nwin; k++)
-        if (!windows[k]) return fail(PYGIM_ERR_INVALID, "null dense part");
-    const bool dev_out = is_device_ptr(out);
-    bool dev_in = is_device_ptr(windows[0]);
-    for (size_t k = 1; k < nwin; k++)
-        if (is_device_ptr(windows[k]) != dev_in) return fail(PYGIM_ERR_INVALID, "dense parts mix host and device memory");
-    if (dev_in != dev_out) return fail(PYGIM_ERR_INVALID, "dense parts and output must both be host or both be device memory");
+// The tunables a call's plan reads (run_plan.hpp), copied in this one place.
+static RunKnobs run_knobs() {
+    RunKnobs k;
+    k.host_windows = g_tune.host_windows; k.host_direct = g_tune.host_direct; k.fuse_windows = g_tune.fuse_windows; k.merge_parts = g_tune.merge_parts;
+    return k;
+}
 
-    // window geometry
-    std::vector<int64_t> rows(nwin), lds(nwin), widths(nwin);
-    {
-        size_t k = 0;
-        if (per_part) {
-            for (auto &p : g->parts)
-                for (size_t j = 0; j < p.dense_cols.size(); j++, k++) {
-                    rows[k] = p.ncols;
-                    widths[k] = p.dense_cols[j];
-                    lds[k] = ld ? ld[k] : p.dense_cols[j];
-                    if (lds[k] < widths[k]) return fail(PYGIM_ERR_INVALID, "window stride smaller than its width");
-                }
-        } else {
-            for (size_t j = 0; j < nwin; j++) {
-                rows[j] = g->total_cols;
-                widths[j] = g->parts[0].dense_cols[j];
-                lds[j] = ld ? ld[j] : widths[j];
-            }
-        }
+// the dense operands of a call: none null, all in host or all in device memory, the output on the same side (each entry point has its own texts)
+struct OperandTexts {
+    const char *null_call, *null_one, *mixed, *sides;
+};
+static int check_dense_operands(const void *const *ops, size_t n, const void *out, const OperandTexts &t, bool *on_device) {
+    if (!ops || !out) return fail(PYGIM_ERR_INVALID, t.null_call);
+    for (size_t k = 0; k < n; k++)
+        if (!ops[k]) return fail(PYGIM_ERR_INVALID, t.null_one);
+    *on_device = is_device_ptr(ops[0]);
+    for (size_t k = 1; k < n; k++)
+        if (is_device_ptr(ops[k]) != *on_device) return fail(PYGIM_ERR_INVALID, t.mixed);
+    if (*on_device != is_device_ptr(out)) return fail(PYGIM_ERR_INVALID, t.sides);
+    return 0;
+}
+
+// Host operands as a pipeline of feature windows, where plan_host_pipeline finds one: asks the device what the plan needs to know, makes room for the
+// gathered windows, runs the pipeline and hands its counts and times to the group.  *done: the call is over (else: the serial path).
+static int run_host_pipeline(Group *g, const RunShape &s, const RunKnobs &knobs, const std::vector<RunWindow> &win, const std::vector<uintptr_t> &addr,
+                             const std::vector<size_t> &off, void *out, hipStream_t st, bool *done) {
+    *done = false;
+    HostFacts f;
+    f.has_merged = g->merged != nullptr;
+    f.copies_slow = g->host_copies_slow;
+    f.stage_out = (uintptr_t)g->stage_out;
+    if (!host_pipeline_eligible(s, knobs, f.has_merged)) return 0;
+    const HostFactsNeeded need = host_facts_needed(s, knobs, f.has_merged, f.copies_slow);
+    if (need.out_pinned) {
+        hipPointerAttribute_t attr;
+        f.out_pinned = hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost;
+        (void)hipGetLastError();
     }
-    std::vector<const void *> dwin(nwin);
+    if (need.out_alias) f.out_alias = (uintptr_t)host_result_on_device(out);
+    Part &m = g->parts.size() == 1 ? g->parts[0] : *g->merged;
+    const HostPlan plan = plan_host_pipeline(s, win.data(), addr.data(), off.data(), knobs, f,
+                                             [&](int64_t w, uintptr_t c) { return lds_writes_c_once(g, m, (uint32_t)w, g->h, (const void *)c); });
+    if (plan.xcat_bytes)
+        if (int rc = ensure(&g->xcat, &g->xcat_bytes, plan.xcat_bytes)) return rc;
+    if (plan.windows.empty()) return 0;
+    double tm[3] = {0, 0, 0};
+    if (int rc = run_group_windows(g, m, plan.windows, g->total_cols, out, plan.direct ? (char *)f.out_alias : nullptr, s.es, st, tm)) return rc;
+    g->host_windows_used = (int64_t)plan.windows.size();
+    g->host_direct_used = plan.direct ? 1 : 0;
+    if (!plan.direct && host_download_was_slow(plan.windows.back().w, s.es, g->total_rows, tm[2])) g->host_copies_slow = true;
+    g->timers[0] = tm[0];
+    g->timers[1] = tm[1];
+    g->timers[2] = tm[2];
+    g->timers[3] = 0;
+    *done = true;
+    return 0;
+}
+
+// shared body of the three run_group flavours: what it does is planned in run_plan.hpp, without a device; here it is done.
+//   windows[k]   : dense operand k (flattened over parts when per_part)
+//   ld[k]        : its row stride in elements
+//   per_part     : grande layout (each window holds only the rows of its own sparse part)
+static int run_group_common(Group *g, const void *const *windows, const int64_t *ld, bool per_part, void *out, hipStream_t st) {
+    // 1. checks and geometry
+    std::vector<RunPart> parts(g->parts.size());
+    for (size_t i = 0; i < parts.size(); i++) parts[i] = {g->parts[i].ncols, g->parts[i].dense_cols.data(), g->parts[i].dense_cols.size()};
+    RunShape s;
+    s.es = dtype_size(g->dtype);
+    s.is_float = g->dtype == PYGIM_FLT32 || g->dtype == PYGIM_DBL64;
+    s.h = g->h; s.total_rows = g->total_rows; s.total_cols = g->total_cols;
+    s.parts = parts.data(); s.nparts = parts.size(); s.per_part = per_part;
+    const size_t es = s.es, nwin = run_window_count(s);
+    static const OperandTexts texts{"null dense operand or output", "null dense part", "dense parts mix host and device memory",
+                                    "dense parts and output must both be host or both be device memory"};
+    bool dev_in = false;
+    if (int rc = check_dense_operands(windows, nwin, out, texts, &dev_in)) return rc;
+    std::vector<RunWindow> win;
+    if (const char *why = run_windows(s, ld, win)) return fail(PYGIM_ERR_INVALID, why);
+    std::vector<uintptr_t> addr(nwin);
+    for (size_t k = 0; k < nwin; k++) addr[k] = (uintptr_t)windows[k];
+    const RunKnobs knobs = run_knobs();
     void *dout = out;
-    double t_in = 0, t_k = 0, t_out = 0;
+    double t_in = 0;
+    // 2. host operands: the pipeline of feature windows where the plan finds one, else one copy up per window
     if (!dev_in) {
         const double t0 = now_ms();
-        size_t total = 0;
-        std::vector<size_t> off(nwin);
-        for (size_t k = 0; k < nwin; k++) {
-            off[k] = total;
-            total += (((size_t)rows[k] * lds[k] * es) + 255) & ~(size_t)255;
-        }
-        if (int rc = ensure(&g->stage_in, &g->stage_in_bytes, std::max<size_t>(total, 256))) return rc;
+        std::vector<size_t> off;
+        if (int rc = ensure(&g->stage_in, &g->stage_in_bytes, host_stage_layout(win.data(), nwin, es, off))) return rc;
         if (int rc = ensure(&g->stage_out, &g->stage_out_bytes, std::max<size_t>((size_t)g->total_rows * g->h * es, 256))) return rc;
-        // the pipeline of feature windows (above): one sparse operand (a single part, or the merged matrix), windows that are column ranges of C
         g->host_windows_used = 1;
         g->host_direct_used = 0;
-        if (g_tune.host_windows != 1 && g->h > 0 && (g->parts.size() == 1 || (!per_part && g->merged && g_tune.merge_parts))) {   // (per-part windows of ONE part: grande)
-            Part &m = g->parts.size() == 1 ? g->parts[0] : *g->merged;
-            std::vector<HostWindow> pw;
-            const size_t xbytes = (size_t)g->total_cols * g->h * es, cbytes = (size_t)g->total_rows * g->h * es;
-            bool automatic = xbytes >= ((size_t)32 << 20) && cbytes >= ((size_t)32 << 20);
-            if (automatic && g_tune.host_windows == 0) {   // (a pitched copy into pageable memory is slower than the serial call)
-                hipPointerAttribute_t attr;
-                automatic = hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost;
-                (void)hipGetLastError();
-            }
-            // DIRECT mode (tunable host_direct): the products store straight into the caller's page-locked tensor -- decided on the full width here, checked
-            // window by window below.  1 = adaptive: the copies first (8.2 ms per call when the DMA engines move the result's windows at the link rate); a call
-            // whose last download ran below 40 GB/s -- the runtime's pitched copies to the host run at 55, 34 or 21 GB/s depending on what the process allocated
-            // and freed before (its DMA-engine bookkeeping; scripts/micro/rect_lottery.hip: the same buffers, the same stream, 34 -> 21 GB/s after the device heap
-            // was churned): the same call then takes 11.8 ms -- turns this group to the direct mode (8.9 ms, whatever the engines do) for its later calls.  2 = always.
-            const int64_t slice_el = std::max<int64_t>(1, 256 / (int64_t)es);
-            char *out_dev = (g_tune.host_direct == 2 || (g_tune.host_direct == 1 && g->host_copies_slow)) ? host_result_on_device(out) : nullptr;
-            if (out_dev && ((((uintptr_t)out_dev) & 255) || (((size_t)g->h * es) & 15) ||
-                            !lds_writes_c_once(g, m, (uint32_t)g->h, g->h, out_dev)))
-                out_dev = nullptr;
-            // the windows: once for the direct mode, again for the copies if a window's product turns out not to be the one-pass LDS-staged kernel
-            for (int attempt = out_dev ? 0 : 1; attempt < 2; attempt++) {
-                pw.clear();
-                if (attempt == 1) out_dev = nullptr;
-                if (nwin == 1 && lds[0] >= widths[0] && widths[0] == g->h) {
-                    // one row-major X: cut into windows of whole 256-byte slices (64 lanes of the LDS-staged product), the wider ones first.  Automatic: 512 bytes
-                    // of a row per window (the DMA engines move such pieces at the 1-D rate; four windows of 256 bytes: 8.8 ms with the copies, 10.2 direct)
-                    const int64_t S = (g->h + slice_el - 1) / slice_el;
-                    const int64_t auto_bytes = 512;
-                    int64_t n = g_tune.host_windows > 1 ? g_tune.host_windows : (automatic ? ((int64_t)g->h * (int64_t)es + auto_bytes - 1) / auto_bytes : 1);
-                    n = std::min<int64_t>(std::min<int64_t>(n, 16), S);
-                    if (n > 1) {
-                        int64_t a = 0;
-                        for (int64_t k = 0; k < n && a < g->h; k++) {
-                            const int64_t w = std::min<int64_t>((S / n + (k < S % n ? 1 : 0)) * slice_el, g->h - a);
-                            pw.push_back({(const char *)windows[0] + (size_t)a * es, lds[0], (size_t)a * es, a, w, {}, 0});
-                            a += w;
-                        }
-                    }
-                } else if (nwin > 1 && (g_tune.host_windows > 1 || automatic)) {
-                    // the caller's own feature blocks (ds_parts; grande's per-unit windows, grande.py:12-23: blocks of `pad` columns of which the first
-                    // widths[k] count): blocks of 512 bytes of a row and more are windows as they are; narrower ones (eight units: 32 floats each) are gathered
-                    // into windows of that size -- each block goes up in one piece and is laid into its columns of xcat on the device
-                    int64_t hsum = 0;
-                    bool narrow = false;
-                    for (size_t k = 0; k < nwin; k++) {
-                        hsum += widths[k];
-                        narrow = narrow || (size_t)widths[k] * es < 512 || lds[k] != widths[k];
-                    }
-                    if (hsum == g->h && !narrow && nwin <= 16) {
-                        int64_t a = 0;
-                        for (size_t k = 0; k < nwin; k++) {
-                            pw.push_back({(const char *)windows[k], lds[k], off[k], a, widths[k], {}, 0});
-                            a += widths[k];
-                        }
-                    } else if (hsum == g->h) {
-                        const int64_t ldc_el = (int64_t)((((size_t)g->h * es + 15) & ~(size_t)15) / es);
-                        if (int rc = ensure(&g->xcat, &g->xcat_bytes, std::max<size_t>((size_t)g->total_cols * ldc_el * es, 256))) return rc;
-                        const int64_t target = g_tune.host_windows > 1 ? (g->h + g_tune.host_windows - 1) / g_tune.host_windows : std::max<int64_t>(1, 512 / (int64_t)es);
-                        int64_t a = 0;
-                        HostWindow cur{nullptr, 0, 0, 0, 0, {}, ldc_el};
-                        for (size_t k = 0; k < nwin; k++) {
-                            cur.pieces.push_back({(const char *)windows[k], lds[k], widths[k], off[k], a});
-                            cur.w += widths[k];
-                            a += widths[k];
-                            if (cur.w >= target || k + 1 == nwin) {
-                                pw.push_back(cur);
-                                cur = HostWindow{nullptr, 0, 0, a, 0, {}, ldc_el};
-                            }
-                        }
-                        if (pw.size() > 16) pw.clear();
-                    }
-                }
-                bool direct_ok = out_dev != nullptr;
-                for (const HostWindow &q : pw)
-                    if (direct_ok && ((((size_t)q.acol * es) & 15) || !lds_writes_c_once(g, m, (uint32_t)q.w, g->h, out_dev + (size_t)q.acol * es))) direct_ok = false;
-                if (direct_ok || attempt == 1) break;
-            }
-            // FLOAT sums on the L2 sweep depend on the product's width (how many lanes share a long row's entries): a window's product would be inside the norm-wise
-            // contract but not the serial call's bits.  Left to itself the library pipelines a float product only where every window is the LDS-staged kernel's
-            // (stored-order sums, or the plan's fixed column ranges: the same bits at any width); host_windows > 1 asks for the windows whatever the kernels.
-            if (g_tune.host_windows == 0 && (g->dtype == PYGIM_FLT32 || g->dtype == PYGIM_DBL64))
-                for (const HostWindow &q : pw)
-                    if (!lds_writes_c_once(g, m, (uint32_t)q.w, g->h, (char *)g->stage_out + (size_t)q.acol * es)) {
-                        pw.clear();
-                        break;
-                    }
-            if (pw.size() > 1) {
-                double tm[3] = {0, 0, 0};
-                if (int rc = run_group_windows(g, m, pw, g->total_cols, out, out_dev, es, st, tm)) return rc;
-                g->host_windows_used = (int64_t)pw.size();
-                g->host_direct_used = out_dev ? 1 : 0;
-                if (!out_dev && pw.back().w > 0 && g->total_rows > 0) {   // (the last window's download, alone on the link: bytes per ms = MB/s x 1e-3)
-                    const double mb = (double)pw.back().w * (double)es * (double)g->total_rows * 1e-6;
-                    if (mb >= 16 && tm[2] > 0 && mb / tm[2] < 40.0) g->host_copies_slow = true;
-                }
-                g->timers[0] = tm[0];
-                g->timers[1] = tm[1];
-                g->timers[2] = tm[2];
-                g->timers[3] = 0;
-                return 0;
-            }
-        }
+        bool done = false;
+        if (int rc = run_host_pipeline(g, s, knobs, win, addr, off, out, st, &done)) return rc;
+        if (done) return 0;
         for (size_t k = 0; k < nwin; k++) {
-            dwin[k] = (char *)g->stage_in + off[k];
-            const size_t bytes = (size_t)rows[k] * lds[k] * es;
-            if (bytes) HIP_TRY(hipMemcpyAsync((void *)dwin[k], windows[k], bytes, hipMemcpyHostToDevice, st));
+            addr[k] = (uintptr_t)g->stage_in + off[k];
+            const size_t bytes = (size_t)win[k].rows * win[k].ld * es;
+            if (bytes) HIP_TRY(hipMemcpyAsync((void *)addr[k], windows[k], bytes, hipMemcpyHostToDevice, st));
         }
         dout = g->stage_out;
         HIP_TRY(hipStreamSynchronize(st));
         t_in = now_ms() - t0;
-    } else {
-        for (size_t k = 0; k < nwin; k++) dwin[k] = windows[k];
     }
     const double t1 = now_ms();
-    // block products: sum over sparse parts, concatenate over dense parts
-    if (g->merged && g_tune.merge_parts && g->parts.size() > 1) {
-        // ... as ONE product with the merged matrix (Group::merged)
-        Part &m = *g->merged;
-        const size_t nd0 = g->parts[0].dense_cols.size();
-        bool in_place = !per_part;  // one window, or windows that sit side by side in one row-major matrix
-        for (size_t j = 1; in_place && j < nd0; j++)
-            in_place = lds[j] == lds[0] && (const char *)dwin[j] == (const char *)dwin[j - 1] + (size_t)widths[j - 1] * es;
-        const char *x = nullptr;
-        int64_t ldx = 0;
-        if (in_place) {
-            x = (const char *)dwin[0];
-            ldx = lds[0];
-        } else {
-            // lay the windows side by side (and, for per-part windows, the parts' row ranges one below the other)
-            const int64_t ldc_el = (int64_t)((((size_t)g->h * es + 15) & ~(size_t)15) / es);
-            const size_t need = (size_t)g->total_cols * ldc_el * es;
-            if (int rc = ensure(&g->xcat, &g->xcat_bytes, std::max<size_t>(need, 256))) return rc;
-            int64_t brow = 0;
-            size_t kbase = 0;
-            for (size_t i = 0; i < g->parts.size(); i++) {
-                Part &p = g->parts[i];
-                int64_t a = 0;
-                for (size_t j = 0; j < p.dense_cols.size(); j++) {
-                    const size_t k = per_part ? kbase + j : j;
-                    const char *src = (const char *)dwin[k] + (per_part ? 0 : (size_t)brow * lds[k] * es);
-                    if (widths[k] > 0 && p.ncols > 0)
-                        HIP_TRY(hipMemcpy2DAsync((char *)g->xcat + ((size_t)brow * ldc_el + (size_t)a) * es, (size_t)ldc_el * es, src,
-                                                 (size_t)lds[k] * es, (size_t)widths[k] * es, (size_t)p.ncols,
-                                                 hipMemcpyDeviceToDevice, st));
-                    a += widths[k];
-                }
-                brow += p.ncols;
-                kbase += p.dense_cols.size();
-            }
-            x = (const char *)g->xcat;
-            ldx = ldc_el;
+    // 3. the block products: windows that are not side by side go into xcat first (the copies of a product, then the product)
+    ProductPlan plan;
+    plan_products(s, win.data(), addr.data(), knobs, g->merged != nullptr, plan);
+    if (plan.xcat_bytes)
+        if (int rc = ensure(&g->xcat, &g->xcat_bytes, plan.xcat_bytes)) return rc;
+    for (const RunProduct &q : plan.products) {
+        for (uint32_t c = q.copy0; c < q.copy1; c++) {
+            const RunCopy &cp = plan.copies[c];
+            if (cp.width > 0 && cp.rows > 0)
+                HIP_TRY(hipMemcpy2DAsync((char *)g->xcat + cp.dst_off, (size_t)q.x.ldx * es, (const char *)addr[cp.win] + cp.src_off, (size_t)win[cp.win].ld * es,
+                                         (size_t)cp.width * es, (size_t)cp.rows, hipMemcpyDeviceToDevice, st));
         }
-        if (int rc = launch_block_any(g, m, x, ldx, dout, g->h, g->h, /*accumulate=*/false, st)) return rc;
-    } else {
-    int64_t brow = 0;
-    size_t kbase = 0;
-    for (size_t i = 0; i < g->parts.size(); i++) {
-        Part &p = g->parts[i];
-        int64_t acol = 0;
-        const size_t nd = p.dense_cols.size();
-        // Several dense windows (ds_parts chunks, grande's per-unit feature windows) are one product of the
-        // full width here: a window is an artefact of the reference's DPU layout, and narrow windows
-        // (32 int8 = 32 bytes) would waste the 128-byte gather.  Windows that already sit side by side in
-        // one row-major matrix are used in place; others are laid side by side first (one 2-D copy each).
-        if (nd > 1 && g_tune.fuse_windows) {
-            const size_t k0 = per_part ? kbase : 0;
-            int64_t wsum = 0;
-            bool adjacent = true;
-            for (size_t j = 0; j < nd; j++) {
-                if (j > 0 && (lds[k0 + j] != lds[k0] ||
-                              (const char *)dwin[k0 + j] != (const char *)dwin[k0 + j - 1] + (size_t)widths[k0 + j - 1] * es))
-                    adjacent = false;
-                wsum += widths[k0 + j];
-            }
-            const char *x = nullptr;
-            int64_t ldx = 0;
-            if (adjacent) {
-                x = (const char *)dwin[k0] + (per_part ? 0 : (size_t)brow * lds[k0] * es);
-                ldx = lds[k0];
-            } else {
-                // row stride rounded up to 16 bytes so that the sweep's 16-byte pieces stay available
-                const int64_t ldc_el = (int64_t)((((size_t)wsum * es + 15) & ~(size_t)15) / es);
-                const size_t need = (size_t)p.ncols * ldc_el * es;
-                if (int rc = ensure(&g->xcat, &g->xcat_bytes, std::max<size_t>(need, 256))) return rc;
-                int64_t a = 0;
-                for (size_t j = 0; j < nd; j++) {
-                    const size_t k = k0 + j;
-                    const char *src = (const char *)dwin[k] + (per_part ? 0 : (size_t)brow * lds[k] * es);
-                    if (widths[k] > 0 && p.ncols > 0)
-                        HIP_TRY(hipMemcpy2DAsync((char *)g->xcat + (size_t)a * es, (size_t)ldc_el * es, src, (size_t)lds[k] * es,
-                                                 (size_t)widths[k] * es, (size_t)p.ncols, hipMemcpyDeviceToDevice, st));
-                    a += widths[k];
-                }
-                x = (const char *)g->xcat;
-                ldx = ldc_el;
-            }
-            if (int rc = launch_block_any(g, p, x, ldx, dout, g->h, wsum, /*accumulate=*/i > 0, st)) return rc;
-        } else
-        for (size_t j = 0; j < nd; j++) {
-            const size_t k = per_part ? kbase + j : j;
-            const int64_t w = widths[k];
-            const char *x = (const char *)dwin[k] + (per_part ? 0 : (size_t)brow * lds[k] * es);
-            char *c = (char *)dout + (size_t)acol * es;
-            if (int rc = launch_block_any(g, p, x, lds[k], c, g->h, w, /*accumulate=*/i > 0, st)) return rc;
-            acol += w;
-        }
-        brow += p.ncols;
-        kbase += p.dense_cols.size();
+        Part &p = q.part < 0 ? *g->merged : g->parts[(size_t)q.part];
+        const void *x = q.x.in_place ? (const void *)q.x.base : g->xcat;
+        if (int rc = launch_block_any(g, p, x, q.x.ldx, (char *)dout + (size_t)q.ccol * es, g->h, q.width, q.accumulate, st)) return rc;
     }
-    }
+    // 4. host operands: the result comes down; the three phases' times
     if (!dev_in) {
         HIP_TRY(hipStreamSynchronize(st));
-        t_k = now_ms() - t1;
-        const double t2 = now_ms();
+        const double t_k = now_ms() - t1, t2 = now_ms();
         const size_t bytes = (size_t)g->total_rows * g->h * es;
         if (bytes) HIP_TRY(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        t_out = now_ms() - t2;
         g->timers[0] = t_in;
         g->timers[1] = t_k;
-        g->timers[2] = t_out;
+        g->timers[2] = now_ms() - t2;
         g->timers[3] = 0;
     }
     return 0;
 }
-
-
 
 // ---- the conv layers' quantiser (models/quantize.py:20-42) in three launches -------------------------
 static bool flat4(const void *a, int64_t ld, uint64_t rows, uint32_t w, const void *b = nullptr) {

@@ -628,6 +628,67 @@ def test_dense_windows_fused_into_one_product(rng, dt):
         assert np.array_equal(od.cpu().numpy(), ref), (dt, widths, "in place")
 
 
+@pytest.mark.parametrize("dt", ["INT32", "FLT32"])
+def test_device_windows_with_gaps_and_side_by_side_under_every_product_plan(rng, dt):
+    """the corners of the product plan (run_plan.hpp plan_products) that the test above leaves open -- it runs host operands under fuse_windows 0 / 1 and
+    per-part device views under the defaults: DEVICE operands, two sparse parts (columns 0..120 and 120..300) x three dense windows of 40 / 33 / 27 columns, under
+    merge_parts 0 / 1 x fuse_windows 0 / 1.  spmm_run_group takes no strides: its windows are three separate blocks of all 300 rows (never side by side).
+    grande_run_group: six per-part windows, once with a stride of width + 3 (gaps: laid into xcat, the second part's below the first's for the merged matrix)
+    and once as views of one row-major matrix (side by side: read in place).  C is pre-filled with 77 so that a column nobody writes shows"""
+    npdt = NP_DTYPES[dt]
+    n, h, bounds, widths = 300, 100, [0, 120, 300], [40, 33, 27]
+    rowptr, col = random_csr(rng, n, n, 10, empty_frac=0.1, long_rows=[(4, 700)])
+    rows_of = np.repeat(np.arange(n), np.diff(rowptr))
+    rp, cl = [], []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        keep = (col >= lo) & (col < hi)
+        rp.append(np.concatenate([[0], np.cumsum(np.bincount(rows_of[keep], minlength=n))]).astype(np.int32))
+        cl.append((col[keep] - lo).astype(np.int32))
+    x = driver_features(rng, n, h, npdt)
+    if dt == "FLT32":
+        x = (x + rng.random((n, h))).astype(npdt)
+    ref = oracle.spmm_csr(rowptr, col, None, x)
+    starts = np.cumsum([0] + widths[:-1])
+    xd = torch.from_numpy(x).cuda()
+    blocks = [xd[:, a:a + w].contiguous() for a, w in zip(starts, widths)]
+    padded, views = [], []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        for a, w in zip(starts, widths):
+            buf = torch.full((hi - lo, w + 3), 99, dtype=xd.dtype, device="cuda")
+            buf[:, :w] = xd[lo:hi, a:a + w]
+            padded.append(buf)
+            views.append(xd.data_ptr() + (lo * h + int(a)) * xd.element_size())
+    st = torch.cuda.current_stream().cuda_stream
+    hd = _lib.group_create(_lib.CSR, CODE[dt], [_ptr(a) for a in rp], [_ptr(a) for a in cl], None, [n, n], [120, 180], [len(c) for c in cl], [3, 3], widths * 2, h)
+    outs = {}
+    try:
+        for merge in (1, 0):
+            for fuse in (1, 0):
+                old = (_lib.set_tunable("merge_parts", merge), _lib.set_tunable("fuse_windows", fuse))
+                try:
+                    calls = {"spmm blocks": lambda o: _lib.spmm_run_group(hd, [b.data_ptr() for b in blocks], o, st),
+                             "grande gaps": lambda o: _lib.grande_run_group(hd, [b.data_ptr() for b in padded], [w + 3 for w in widths] * 2, o, st),
+                             "grande views": lambda o: _lib.grande_run_group(hd, views, [h] * 6, o, st)}
+                    for name, call in calls.items():
+                        od = torch.full((n, h), 77, dtype=xd.dtype, device="cuda")
+                        call(od.data_ptr())
+                        torch.cuda.synchronize()
+                        outs[(name, merge, fuse)] = od.cpu().numpy()
+                finally:
+                    _lib.set_tunable("merge_parts", old[0])
+                    _lib.set_tunable("fuse_windows", old[1])
+    finally:
+        _lib.group_free(hd)
+    assert len(outs) == 12
+    scale = abs_scale(rowptr, col, None, x)
+    for key, got in outs.items():
+        if dt == "INT32":
+            assert np.array_equal(got, ref), key
+            assert np.array_equal(got, outs[("spmm blocks", 1, 1)]), key
+        else:
+            assert np.all(np.abs(got.astype(np.float64) - ref.astype(np.float64)) <= 1e-5 * scale + 1e-30), key
+
+
 @pytest.mark.parametrize("dt", ALL_DTYPES)
 @pytest.mark.parametrize("group_slices", [1, 3])
 def test_panel_sweep_in_slice_groups(rng, dt, group_slices):
