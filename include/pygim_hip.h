@@ -510,17 +510,61 @@ int pygim_spmm_multi_reduce(int dtype, const int *stats /* host, 1..6 distinct *
                             void *out /* [nrows, nstats * h] */, int64_t ldo, int32_t *arg_max, int32_t *arg_min /* [nrows, h] or NULL */,
                             void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- softmax aggregation per feature in one gather (PyG's SoftmaxAggregation: GENConv / DeeperGCN, aggr = "softmax") ----
+ *   pygim_spmm_softmax:  with s[e, f] = t[f] * X[colind[e], f] over the stored entries e of row r (unit weights: no values operand)
+ *       lse[r, f] = log sum_e exp(s[e, f])      p[e, f] = exp(s[e, f] - lse[r, f])      out[r, f] = sum_e p[e, f] * X[colind[e], f]
+ *     t: [h] on the device, a temperature per feature (0: the mean; large: towards the max).  lse: [nrows, h] contiguous, or NULL.
+ *     One pass over the stored entries: per feature a lane carries the online-softmax triple (maximum, denominator, numerator) beside
+ *     one gather of X, one exp per element and entry; nothing of size nnz * h exists.  Duplicates count separately.
+ *     The contract of pygim_spmm_multi_reduce: device pointers only, a valid CSR guaranteed by the caller, nnz = 0, nrows = 0, empty rows
+ *     and any h >= 1 allowed, row strides ldx >= h and ldo >= h (columns of out beyond h are not touched), work is only enqueued on
+ *     `stream`, scratch from the caller (pygim_spmm_softmax_workspace bytes: a function of its arguments alone, -1 for bad arguments;
+ *     16-byte aligned; per run of 512 entries two slots of h elements of each of the three components, every sub-array 16-byte aligned),
+ *     no atomics, no two kernels write the same row, the same bits on every launch, and out has the same bits with and without lse.
+ *     Empty rows store 0, and -inf in lse.
+ *     Types: FLT32 and DBL64 compute in themselves.  FLT16 / BF16: X and out are stored in 16 bits, an element is widened as it is
+ *       folded (exact); t, lse, the triple and every intermediate are float32; out is rounded once, where the row is stored.
+ *     Non-finite inputs: a (row, feature) that gathers a NaN or +-inf score stores a non-finite out (NaN or +-inf, never a finite
+ *       number; its lse is unspecified); entries are never skipped.  Every other (row, feature) keeps the bits it has when that
+ *       element is replaced by 0.
+ *     Bounds, in the form of pygim_sparse_attention, with EPS = 1e-5 (float32 arithmetic) or 1e-12 (DBL64) and
+ *     Delta[r, f] = EPS * max_e |s[e, f]|:
+ *       |out - exact| <= (2 EPS + 2 Delta) * sum_e p[e] |x[e]|      (+ u |exact| for 16-bit out, u = 2^-8 BF16 / 2^-11 FLT16)
+ *       |lse - exact| <= 2 EPS (1 + |exact|) + Delta
+ *     (float32 arithmetic takes exp(x), x <= 0, as the hardware exponential of x * log2(e): a relative error of about |x| 2^-24,
+ *     which is what Delta allows for; DBL64 calls exp.)
+ *   pygim_spmm_softmax_backward:  one gather on the CSR of A^T (rowptr_t [ncols + 1], rows_t [nnz]: the A-row of every entry; no
+ *     permutation, nothing of size nnz allocated).  For an entry of column c that belongs to A-row r:
+ *       p = exp(t[f] * X[c, f] - lse[r, f])     a[c, f] = sum G[r, f] * p     b[c, f] = sum G[r, f] * p * (X[c, f] - out[r, f])
+ *       dX[c, f] = a + t[f] * b                 dT[c, f] = X[c, f] * b        (dT: [ncols, h] contiguous, or NULL)
+ *     The gradient of t is the column sum of dT, formed by the caller (= sum_r G * (E_p[x^2] - out^2)).  out and lse are what the forward
+ *     stored ([.., ldo] and [nrows, h] contiguous).  The partial result is the two plain sums a and b in stored order (workspace: two
+ *     slots of h elements of each per run).  dX has the same bits with and without dT; columns without entries get zeros.
+ *     FLT16 / BF16: X, G, out and dX are 16-bit (out the stored, once-rounded one), t, lse, dT and all sums float32.
+ *     Determinism, stream and scratch rules as for the forward.
+ *   PYGIM_ERR_INVALID (both): an integer type, h > 65535 * 128, a row stride below h, a workspace that is too small or misaligned. */
+int64_t pygim_spmm_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h);
+int pygim_spmm_softmax(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X, int64_t ldx,
+                       const void *t /* [h] device */, int64_t h, void *out, int64_t ldo, void *lse /* [nrows, h] contiguous or NULL */,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int64_t pygim_spmm_softmax_backward_workspace(int dtype, int64_t ncols, int64_t nnz, int64_t h);
+int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_t, const int32_t *rows_t, int64_t nnz, const void *X,
+                                int64_t ldx, const void *t, int64_t h, const void *G, int64_t ldg, const void *out, int64_t ldo,
+                                const void *lse, void *dX, int64_t ldd, void *dT /* [ncols, h] contiguous or NULL */, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+
 /* ---- which kernel instantiation and lane layout a call of the entry points above gets ----
  * The decision their launchers take, from the host functions the launchers themselves call: no device is touched and nothing is
  * launched (like the *_workspace functions it works without a GPU and without pygim_init_*).  `kind` names the entry point, `dtype`
  * the storage type, `aligned` != 0 says that every row stride is a multiple of a 16-byte piece and every base pointer (the
  * workspace included) a multiple of 16 bytes.  heads is ignored by SDDMM, SPMM_REDUCE and SPMM_REDUCE_BACKWARD, h by EDGE_SOFTMAX;
  * SPMM_MULTI_REDUCE (FLT32, DBL64, FLT16, BF16: the lane layout of the mean fold, whatever the statistics) has no heads and takes
- * heads = 1 alone (anything else: PYGIM_ERR_INVALID)
+ * heads = 1 alone (anything else: PYGIM_ERR_INVALID); so do SPMM_SOFTMAX and SPMM_SOFTMAX_BACKWARD (the same types and the same lane
+ * layout; `aligned` covers lse as well for the backward)
  * (forward and backward are one kind: the backward only has one more pointer that must be aligned).
  *   out[0] vec       features per piece (per lane and load): 16 / element size, or 1
  *   out[1] pieces    pieces a lane holds at once: 1 or 2 (row walkers: SPMM_VALUES, SPMM_REDUCE, GAT_AGGREGATE, SPMM_REDUCE_BACKWARD,
- *                    SPMM_MULTI_REDUCE),
+ *                    SPMM_MULTI_REDUCE, SPMM_SOFTMAX, SPMM_SOFTMAX_BACKWARD),
  *                    1, 2 or 4 (head-wise: SPARSE_ATTENTION, GATV2_*), 1 .. 4 (SDDMM), 1 (EDGE_SOFTMAX)
  *   out[2] LH        lanes across the features of one head (head-wise kernels); L for the others
  *   out[3] L         lanes per entry (a power of two; 64 / L entries side by side in a wave)
@@ -536,8 +580,8 @@ int pygim_spmm_multi_reduce(int dtype, const int *stats /* host, 1..6 distinct *
  *                                            heads, `heads` for EDGE_SOFTMAX) does not fill whole pieces / `aligned` is 0
  * Returns PYGIM_ERR_INVALID for what the entry point itself rejects for these numbers: an unknown kind, a type it does not take,
  * heads not dividing h, h / heads > 256 (head-wise), and h > 65535 * 128 for the row walkers -- one launch holds 65535 chunks, so
- * pygim_spmm_values, pygim_spmm_reduce, pygim_spmm_multi_reduce, pygim_gat_aggregate, their *_workspace functions (-1) and pygim_spmm_reduce_backward
- * reject a wider row before any launch, whatever the alignment.                                                               */
+ * pygim_spmm_values, pygim_spmm_reduce, pygim_spmm_multi_reduce, pygim_spmm_softmax, pygim_spmm_softmax_backward, pygim_gat_aggregate, their
+ * *_workspace functions (-1) and pygim_spmm_reduce_backward reject a wider row before any launch, whatever the alignment.                                                               */
 #define PYGIM_SHAPE_SPMM_VALUES 0
 #define PYGIM_SHAPE_SPMM_REDUCE 1
 #define PYGIM_SHAPE_GAT_AGGREGATE 2
@@ -548,6 +592,8 @@ int pygim_spmm_multi_reduce(int dtype, const int *stats /* host, 1..6 distinct *
 #define PYGIM_SHAPE_EDGE_SOFTMAX 7
 #define PYGIM_SHAPE_SPMM_REDUCE_BACKWARD 8
 #define PYGIM_SHAPE_SPMM_MULTI_REDUCE 9
+#define PYGIM_SHAPE_SPMM_SOFTMAX 10
+#define PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD 11
 #define PYGIM_SHAPE_PART_PIECE 1
 #define PYGIM_SHAPE_PART_CHUNK 2
 #define PYGIM_SHAPE_PART_HEADS 4

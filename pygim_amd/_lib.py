@@ -26,6 +26,7 @@ EXPORTS = [
     "pygim_gatv2_aggregate", "pygim_gatv2_aggregate_workspace", "pygim_gatv2_backward", "pygim_gatv2_backward_workspace",
     "pygim_spmm_reduce", "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward", "pygim_gather_launch_shape",
     "pygim_spmm_multi_reduce", "pygim_spmm_multi_reduce_workspace",
+    "pygim_spmm_softmax", "pygim_spmm_softmax_workspace", "pygim_spmm_softmax_backward", "pygim_spmm_softmax_backward_workspace",
     "pygim_gat_aggregate_dropout", "pygim_sparse_attention_dropout", "pygim_gatv2_aggregate_dropout", "pygim_gatv2_backward_dropout",
     "pygim_attention_dropout_mask", "pygim_attention_dropout_host",
 ]
@@ -38,10 +39,10 @@ REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
 STAT_SUM, STAT_MEAN, STAT_MIN, STAT_MAX, STAT_VAR, STAT_STD = range(6)   # pygim_spmm_multi_reduce
 # pygim_gather_launch_shape: the kinds, the names of out[0..7] and the bits of "flags"
 (SHAPE_SPMM_VALUES, SHAPE_SPMM_REDUCE, SHAPE_GAT_AGGREGATE, SHAPE_SPARSE_ATTENTION, SHAPE_GATV2_AGGREGATE, SHAPE_GATV2_BACKWARD, SHAPE_SDDMM,
- SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD, SHAPE_SPMM_MULTI_REDUCE) = range(10)
+ SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD, SHAPE_SPMM_MULTI_REDUCE, SHAPE_SPMM_SOFTMAX, SHAPE_SPMM_SOFTMAX_BACKWARD) = range(12)
 SHAPE_FIELDS = ("vec", "pieces", "LH", "L", "per", "chunks", "launches", "flags")
 SHAPE_PART_PIECE, SHAPE_PART_CHUNK, SHAPE_PART_HEADS, SHAPE_SCALAR_SIZE, SHAPE_SCALAR_ALIGN = 1, 2, 4, 8, 16
-GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, spmm_multi_reduce, gat_aggregate and spmm_reduce_backward
+GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, spmm_multi_reduce, spmm_softmax, gat_aggregate and spmm_reduce_backward
 
 
 class PygimError(RuntimeError):
@@ -115,6 +116,12 @@ def lib():
         L.pygim_spmm_multi_reduce_workspace.argtypes = [c_int, p_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_multi_reduce_workspace.restype = c_i64
         L.pygim_spmm_multi_reduce.argtypes = [c_int, p_int, c_int, ctypes.c_double, c_i64, vp, vp, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, vp, vp, c_i64, vp]
+        L.pygim_spmm_softmax_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_softmax_workspace.restype = c_i64
+        L.pygim_spmm_softmax.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_spmm_softmax_backward_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_softmax_backward_workspace.restype = c_i64
+        L.pygim_spmm_softmax_backward.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -434,6 +441,38 @@ def spmm_multi_reduce(dtype, stats, eps, nrows, rowptr_ptr, col_ptr, nnz, x_ptr,
     arr, k = _stat_array(stats)
     check(lib().pygim_spmm_multi_reduce(int(dtype), arr, k, float(eps), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr), int(ldx), int(h),
                                         _vp(out_ptr), int(ldo), _vp(arg_max_ptr), _vp(arg_min_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def spmm_softmax_workspace(dtype, nrows, nnz, h):
+    """bytes of scratch spmm_softmax needs for this type and shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_softmax_workspace(int(dtype), int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_softmax_workspace arguments")
+    return n
+
+
+def spmm_softmax(dtype, nrows, rowptr_ptr, col_ptr, nnz, x_ptr, ldx, t_ptr, h, out_ptr, ldo, lse_ptr, ws_ptr, ws_bytes, stream=0):
+    """out[r, f] = sum over the entries e of row r of softmax_e(t[f] * X[col[e], f]) * X[col[e], f], in one gather; t_ptr: [h] in the compute
+    type; lse_ptr: [nrows, h] in the compute type for the log-sum-exp, or 0 (FLT32, DBL64, FLT16, BF16)"""
+    check(lib().pygim_spmm_softmax(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr), int(ldx), _vp(t_ptr), int(h),
+                                   _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def spmm_softmax_backward_workspace(dtype, ncols, nnz, h):
+    """bytes of scratch spmm_softmax_backward needs for this type and shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_softmax_backward_workspace(int(dtype), int(ncols), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_softmax_backward_workspace arguments")
+    return n
+
+
+def spmm_softmax_backward(dtype, ncols, rowptr_t_ptr, rows_t_ptr, nnz, x_ptr, ldx, t_ptr, h, g_ptr, ldg, out_ptr, ldo, lse_ptr, dx_ptr, ldd, dt_ptr,
+                          ws_ptr, ws_bytes, stream=0):
+    """the gradient of spmm_softmax in one gather on the CSR of A^T: dX [ncols, h] and, when dt_ptr is not 0, dT [ncols, h] in the compute
+    type, whose column sum is the gradient of t; out_ptr / lse_ptr: what the forward stored"""
+    check(lib().pygim_spmm_softmax_backward(int(dtype), int(ncols), _vp(rowptr_t_ptr), _vp(rows_t_ptr), int(nnz), _vp(x_ptr), int(ldx), _vp(t_ptr), int(h),
+                                            _vp(g_ptr), int(ldg), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(dx_ptr), int(ldd), _vp(dt_ptr), _vp(ws_ptr),
+                                            int(ws_bytes), _vp(stream)))
 
 
 def gather_launch_shape(kind, dtype, h, heads=1, aligned=True):

@@ -213,6 +213,15 @@ class SparseGroupBase:
 
         return matmul_multi_reduce(self, B, reduces, eps)
 
+    def mul_softmax(self, B: torch.Tensor, t=1.0):
+        """softmax aggregation of B per row and feature on the raw tensor's structure with unit weights,
+        ``out[r, f] = sum_e softmax_e(t[f] * B[col[e], f]) * B[col[e], f]`` (``pygim_amd.reduce.spmm_softmax``: PyG's ``aggr="softmax"``),
+        from one gather.  t: a float, a 0-d tensor or ``[h]``.  No group is created or used.  Differentiable in B and t
+        (float32 / float64 / bfloat16 / float16)."""
+        from ..reduce import matmul_softmax
+
+        return matmul_softmax(self, B, t)
+
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):
         assert nparts > 0

@@ -33,6 +33,7 @@
 #include "gatv2_dev.hpp"
 #include "spmm_reduce_dev.hpp"
 #include "spmm_multi_dev.hpp"
+#include "spmm_softmax_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -595,7 +596,7 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
 
 }  // extern "C"
 
-// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward, spmm_multi_reduce ----
+// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward, spmm_multi_reduce, spmm_softmax and its backward ----
 // f(T()) with T the element type of `dtype` (the caller has checked it); INTS = false: FLT32 / DBL64 only
 template <bool INTS = false, typename F> static void with_elem_type(int dtype, F &&f) {
     if constexpr (INTS) {
@@ -1105,6 +1106,60 @@ int pygim_spmm_multi_reduce(int dtype, const int *stats, int nstats, double eps,
     return 0;
 }
 
+int64_t pygim_spmm_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h) {
+    if (!is_gather_type(dtype) || nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
+    return (int64_t)softmax_workspace_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
+}
+
+int pygim_spmm_softmax(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X, int64_t ldx, const void *t,
+                       int64_t h, void *out, int64_t ldo, void *lse, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_softmax: type must be FLT32, DBL64, FLT16 or BF16");
+    if (int rc = check_csr_call("spmm_softmax", "rowptr / colind / X / t / out / lse", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {t, nnz > 0}},
+                                pygim_spmm_softmax_workspace(dtype, nrows, nnz, h), workspace, workspace_bytes))
+        return rc;
+    if (lse && (uintptr_t)lse % gather_compute_size(dtype) != 0) return fail(PYGIM_ERR_INVALID, "spmm_softmax: lse must be aligned to its element");
+    with_gather_types(dtype, [&](auto tt, auto s) {
+        using T = decltype(tt);
+        using S = decltype(s);
+        launch_spmm_softmax<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)X, (uint64_t)ldx, (const T *)t,
+                                  (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_spmm_softmax_backward_workspace(int dtype, int64_t ncols, int64_t nnz, int64_t h) {
+    if (!is_gather_type(dtype) || ncols < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
+    return (int64_t)softmax_backward_workspace_bytes((uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
+}
+
+int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_t, const int32_t *rows_t, int64_t nnz, const void *X, int64_t ldx,
+                                const void *t, int64_t h, const void *G, int64_t ldg, const void *out, int64_t ldo, const void *lse, void *dX, int64_t ldd,
+                                void *dT, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = need_init()) return rc;
+    if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "spmm_softmax_backward: type must be FLT32, DBL64, FLT16 or BF16");
+    if (h >= 1 && (ldg < h || ldo < h)) return fail(PYGIM_ERR_INVALID, "bad spmm_softmax_backward sizes / strides");
+    if (int rc = check_csr_call("spmm_softmax_backward", "rowptr_t / rows_t / X / t / G / out / lse / dX / dT", ncols, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H,
+                                ldx, ldd,
+                                {{rowptr_t, true}, {dX, ncols > 0}, {dT, ncols > 0, true}, {rows_t, nnz > 0}, {X, nnz > 0}, {t, nnz > 0}, {G, nnz > 0},
+                                 {out, nnz > 0}, {lse, nnz > 0}},
+                                pygim_spmm_softmax_backward_workspace(dtype, ncols, nnz, h), workspace, workspace_bytes))
+        return rc;
+    if ((nnz > 0 && (uintptr_t)lse % gather_compute_size(dtype) != 0) || (dT && (uintptr_t)dT % gather_compute_size(dtype) != 0))
+        return fail(PYGIM_ERR_INVALID, "spmm_softmax_backward: lse and dT must be aligned to their element");
+    with_gather_types(dtype, [&](auto tt, auto s) {
+        using T = decltype(tt);
+        using S = decltype(s);
+        launch_spmm_softmax_backward<T, S>((const uint32_t *)rowptr_t, (const uint32_t *)rows_t, (uint32_t)ncols, (uint32_t)nnz, (const S *)X, (uint64_t)ldx,
+                                           (const T *)t, (uint32_t)h, (const S *)G, (uint64_t)ldg, (const S *)out, (uint64_t)ldo, (const T *)lse, (S *)dX,
+                                           (uint64_t)ldd, (T *)dT, workspace, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the launch shape of a gather entry point, from the functions its launcher calls; no device, no launch (like the *_workspace functions)
 int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int aligned, int64_t out[8]) {
     static_assert(LS_PART_PIECE == PYGIM_SHAPE_PART_PIECE && LS_PART_CHUNK == PYGIM_SHAPE_PART_CHUNK && LS_PART_HEADS == PYGIM_SHAPE_PART_HEADS &&
@@ -1113,7 +1168,8 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     if (!out) return PYGIM_ERR_INVALID;
     const bool head_wise = kind == PYGIM_SHAPE_SPARSE_ATTENTION || kind == PYGIM_SHAPE_GATV2_AGGREGATE || kind == PYGIM_SHAPE_GATV2_BACKWARD;
     const bool walker = kind == PYGIM_SHAPE_SPMM_VALUES || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_GAT_AGGREGATE ||
-                        kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD || kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE;
+                        kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD || kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE || kind == PYGIM_SHAPE_SPMM_SOFTMAX ||
+                        kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD;
     bool type_ok;
     if (kind == PYGIM_SHAPE_SPMM_REDUCE) type_ok = dtype_size(dtype) != 0 || is_half_type(dtype);   // integers: max / min; 16-bit: the mean
     else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) type_ok = is_float_type(dtype);
@@ -1121,6 +1177,7 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     if (!(head_wise || walker || kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_EDGE_SOFTMAX) || !type_ok) return PYGIM_ERR_INVALID;
     if (kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) heads = 1;   // they have none
     if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE && heads != 1) return PYGIM_ERR_INVALID;   // it has none either, and says so: heads must be 1
+    if ((kind == PYGIM_SHAPE_SPMM_SOFTMAX || kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD) && heads != 1) return PYGIM_ERR_INVALID;   // nor have these
     if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) h = heads;                                                                           // it has no h
     if (h < 1 || heads < 1 || heads > 0x7FFFFFFFll || h % heads != 0 || h > (walker ? (int64_t)RG_MAX_H : 0xFFFFFFFFll)) return PYGIM_ERR_INVALID;
     if (head_wise && h / heads > (int64_t)SA_MAX_HEAD) return PYGIM_ERR_INVALID;
@@ -1131,6 +1188,8 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) g = edge_softmax_shape((uint32_t)heads, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) g = spmm_reduce_bwd_shape((uint32_t)h, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE) g = multi_gather_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_SOFTMAX) g = softmax_gather_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD) g = softmax_grad_shape((uint32_t)h, V, aligned != 0);
     else g = row_gather_shape((uint32_t)h, (uint32_t)(h / heads), V, aligned != 0);
     const int64_t v[8] = {g.vec, g.npl, g.LH, g.L, g.per, g.chunks, g.launches, g.flags};
     for (int i = 0; i < 8; i++) out[i] = v[i];

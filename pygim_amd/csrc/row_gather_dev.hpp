@@ -23,11 +23,12 @@
 //
 // What the siblings share with this file, and what they do not:
 //   * rg_cut_row -- which row goes on after run w, and up to which run -- is the preamble of k_row_gather_fixup, k_gat_fixup
-//     (gat_aggregate_dev.hpp) and k_multi_fixup (spmm_multi_dev.hpp); rg_dispatch is the host's choice between the three launch forms
-//     of row_gather_shape for launch_row_gather_v, launch_gat_gather_v and launch_multi_gather_v.
+//     (gat_aggregate_dev.hpp), k_multi_fixup (spmm_multi_dev.hpp), k_softmax_fixup and k_softmax_grad_fixup (spmm_softmax_dev.hpp);
+//     rg_dispatch is the host's choice between the three launch forms of row_gather_shape for launch_row_gather_v, launch_gat_gather_v,
+//     launch_multi_gather_v, launch_softmax_gather_v and launch_softmax_grad_v.
 //   * The walk inside the gather kernel -- batch loop, row search, ballot of row ends, cut into stretches, slot rule -- is still copied
-//     text in k_gat_gather, k_multi_gather, k_sa_gather (sparse_attention_dev.hpp), k_gatv2_gather and k_gatv2_grad (gatv2_dev.hpp):
-//     a change to the walk here has to be made in those five as well.  One device function for it, taking the kernel's per-batch
+//     text in k_gat_gather, k_multi_gather, k_sa_gather (sparse_attention_dev.hpp), k_gatv2_gather and k_gatv2_grad (gatv2_dev.hpp),
+//     k_softmax_gather and k_softmax_grad (spmm_softmax_dev.hpp): a change to the walk here has to be made in those seven as well.  One device function for it, taking the kernel's per-batch
 //     load, its fold of a stretch and its row close as three lambdas, was written and measured (profiles/walker_refactor_resources.txt):
 //     every call inlines and no form uses scratch, but a fold body that is optimised as a function of its own before it is inlined does
 //     not come out as the same body written in the kernel, and in every form tried some instantiations lose a wave per SIMD (27 of
@@ -374,7 +375,7 @@ inline LaunchShape row_gather_shape(uint32_t h, uint32_t width, uint32_t V, bool
     return g;
 }
 
-// the three launch forms of a row_gather_shape, for k_row_gather, k_gat_gather and k_multi_gather alike:
+// the three launch forms of a row_gather_shape, for k_row_gather, k_gat_gather, k_multi_gather, k_softmax_gather and k_softmax_grad alike:
 // launch(integral_constant<int, NV>, bool_constant<WHOLE>, grid, L) starts the kernel's <.., NV, WHOLE, ..> form on that grid
 template <typename Launch> inline void rg_dispatch(uint64_t nnz, const LaunchShape &g, Launch &&launch) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);

@@ -29,6 +29,10 @@ tensors; the same dtypes as GATConv.
 PNAConv / PNA are PyG's PNAConv with one tower, one linear pre-layer and no edge features on ``pygim_amd.reduce.spmm_multi_reduce``:
 mean, min, max and std (or any of sum / mean / min / max / var / std) of the neighbours' messages come from one gather per layer, no
 ``[E, F]`` message tensor is formed; identity / amplification / attenuation scalers; float32 / float64, bfloat16 like ``SAGEConv(aggr="mean")``.
+
+GENConv / GEN are PyG's GENConv (DeeperGCN, Li et al.) without edge features on ``pygim_amd.reduce.spmm_softmax``: the softmax aggregation
+of the neighbours' messages per feature, with a fixed or learnable temperature, is one gather per layer forward and one backward, no
+``[E, F]`` tensor; ``aggr="mean"`` / ``"max"`` / ``"sum"`` go through the functions that exist; the same dtypes as PNAConv.
 """
 import torch
 import torch.nn.functional as F
@@ -267,6 +271,73 @@ class PNAConv(torch.nn.Module):
         return self.lin(self.post_nn(torch.cat([x, torch.cat(outs, 1)], 1)))
 
 
+class GENConv(torch.nn.Module):
+    """PyG's GENConv (Li et al., DeeperGCN) without edge features, on the adjacency as given:
+    message of stored entry (i, j) = relu(x_src[j]) + eps;  agg_i = the aggregation of the messages over the entries of row i;
+    out = mlp(agg + x_dst),  x_src = lin_src(x) and x_dst = lin_dst(x) when ``in_channels != out_channels`` (else x itself),
+    mlp = Linear -> norm -> ReLU -> Linear (``num_layers`` linear maps, hidden width ``expansion * out_channels``).
+
+    Without edge features the message depends on the source node alone, so it is formed per node and no ``[E, F]`` tensor exists.
+    ``aggr="softmax"``: ``agg_i[f] = sum_j softmax_j(t * msg_j[f]) * msg_j[f]`` with the temperature ``t`` (a parameter with
+    ``learn_t``), ONE ``spmm_softmax`` gather (``fused=True``, the default: the composition holds ``[nnz, out_channels]`` tensors) or its
+    composition from ``edge_softmax`` and ``spmm_values`` (``fused=False``).  ``"mean"``, ``"max"``, ``"sum"``: ``spmm_reduce`` /
+    ``spmm_values`` with unit weights.  Rows without entries aggregate to 0.
+    float32 / float64, trainable; bfloat16 after ``.to(torch.bfloat16)`` or under ``torch.autocast`` (softmax, mean, sum); one GPU."""
+
+    def __init__(self, in_channels, out_channels, aggr="softmax", t=1.0, learn_t=False, eps=1e-7, num_layers=2, expansion=2, norm="batch", bias=True,
+                 fused=True, edge_dim=None, learn_p=False, msg_norm=False, **_):
+        super().__init__()
+        if aggr in ("powermean", "power"):
+            raise NotImplementedError("GENConv: aggr='powermean' is not implemented (softmax, mean, max and sum are)")
+        if edge_dim is not None:
+            raise NotImplementedError("GENConv: edge features (edge_dim) are not implemented")
+        if learn_p or msg_norm:
+            raise NotImplementedError("GENConv: learn_p and msg_norm are not implemented")
+        if aggr not in ("softmax", "mean", "max", "sum", "add"):
+            raise ValueError(f"GENConv: aggr must be 'softmax', 'mean', 'max' or 'sum', got {aggr!r}")
+        if norm not in ("batch", "layer", None):
+            raise ValueError(f"GENConv: norm must be 'batch', 'layer' or None, got {norm!r}")
+        self.aggr = "sum" if aggr == "add" else aggr
+        self.in_channels, self.out_channels, self.eps, self.fused = int(in_channels), int(out_channels), float(eps), bool(fused)
+        self.lin_src = self.lin_dst = None
+        if self.in_channels != self.out_channels:
+            self.lin_src = Linear(self.in_channels, self.out_channels, bias=bias)
+            self.lin_dst = Linear(self.in_channels, self.out_channels, bias=bias)
+        if learn_t and self.aggr == "softmax":
+            self.t = torch.nn.Parameter(torch.tensor(float(t)))
+        else:
+            self.t = float(t)
+        widths = [self.out_channels] + [self.out_channels * int(expansion)] * (int(num_layers) - 1) + [self.out_channels]
+        layers = []
+        for i in range(len(widths) - 1):
+            layers.append(Linear(widths[i], widths[i + 1], bias=bias))
+            if i < len(widths) - 2:
+                if norm is not None:
+                    layers.append(BatchNorm1d(widths[i + 1]) if norm == "batch" else torch.nn.LayerNorm(widths[i + 1]))
+                layers.append(ReLU())
+        self.mlp = Sequential(*layers)
+
+    def forward(self, x, adj_t, edge_attr=None):
+        if edge_attr is not None:
+            raise NotImplementedError("GENConv: edge features are not implemented")
+        if getattr(adj_t, "row_sharded", False):
+            raise NotImplementedError("GENConv is not available on a RowShardAdj (one GPU only)")
+        from .attention import EdgeGraph, _compute_dtype, spmm_values
+        from .reduce import spmm_reduce, spmm_softmax
+
+        g = EdgeGraph.of(adj_t)
+        src = x if self.lin_src is None else self.lin_src(x)
+        msg = F.relu(src) + self.eps
+        if self.aggr == "softmax":
+            agg = spmm_softmax(g, msg, self.t, fused=self.fused)
+        elif self.aggr == "sum":
+            agg = spmm_values(g, torch.ones(g.nnz, dtype=_compute_dtype(msg.dtype), device=msg.device), msg)
+        else:
+            agg = spmm_reduce(g, msg, self.aggr)
+        dst = x if self.lin_dst is None else self.lin_dst(x)
+        return self.mlp(agg + dst.to(agg.dtype))
+
+
 def _att_dropout(name, p):
     """a layer's ``dropout=`` (attention dropout, as in PyG): a rate in [0, 1), active only while the layer is training"""
     p = float(p)
@@ -346,6 +417,13 @@ class PNA(_Stack):
                  scalers=("identity", "amplification", "attenuation"), deg=None, post_layers=1, fused=None):
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
                          lambda h: PNAConv(h, h, aggregators=aggregators, scalers=scalers, deg=deg, post_layers=post_layers, fused=fused))
+
+
+class GEN(_Stack):
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, aggr="softmax", t=1.0, learn_t=False, norm="batch",
+                 fused=True):
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: GENConv(h, h, aggr=aggr, t=t, learn_t=learn_t, norm=norm, fused=fused))
 
 
 class GraphTransformer(_Stack):

@@ -1,5 +1,6 @@
-"""Aggregation with a reduction other than the sum: ``spmm_reduce`` (mean / max / min over the stored entries of every row) and
-``spmm_multi_reduce`` (several statistics of the same neighbourhood -- sum, mean, min, max, var, std -- from ONE gather).
+"""Aggregation with a reduction other than the sum: ``spmm_reduce`` (mean / max / min over the stored entries of every row),
+``spmm_multi_reduce`` (several statistics of the same neighbourhood -- sum, mean, min, max, var, std -- from ONE gather) and
+``spmm_softmax`` (PyG's SoftmaxAggregation: a softmax per row and feature with the feature as its own score, in ONE gather).
 
 ``torch_sparse.matmul(adj, x, reduce=...)`` with ``"mean"``, ``"max"`` or ``"min"``: GraphSAGE's mean, max-pool SAGE, PNA- and GIN-style
 layers.  A reduction other than the sum cannot be compiled into a device group, so this is a functional entry point on the plain CSR
@@ -19,8 +20,13 @@ run).  Sums stay with ``mul`` / ``spmm_values``.
   var = max(mean(x^2) - mean(x)^2, 0), std = sqrt(var + eps); differentiable in X through kernels that exist (``spmm_values`` on the
   transposed structure, pygim_spmm_reduce_backward); ``fused=False`` composes the same result from ``spmm_reduce`` calls.
 
+* ``spmm_softmax``: ``out[r, f] = sum_e softmax_e(t[f] * x[e, f]) * x[e, f]`` with a temperature per feature (pygim_spmm_softmax: the
+  online-softmax triple per feature beside one gather of X; pygim_spmm_softmax_backward: one gather on the transposed structure that
+  takes the probabilities again from the saved log-sum-exp).  float32 / float64 / bfloat16 / float16; differentiable in X and t;
+  ``fused=False`` composes it from ``edge_softmax`` and ``spmm_values`` with ``heads = h`` through ``[nnz, h]`` tensors.
+
 Not covered: the gradient of max / min with respect to ``value`` (it needs a masked SDDMM), double backward, integer mean,
-multi-head values, edge weights or integer types in ``spmm_multi_reduce``, ``RowShardAdj`` / multi-GPU.
+multi-head values, edge weights or integer types in ``spmm_multi_reduce`` and ``spmm_softmax``, ``RowShardAdj`` / multi-GPU.
 """
 from __future__ import annotations
 
@@ -342,3 +348,102 @@ def spmm_multi_reduce(graph, X: torch.Tensor, reduces=("mean", "min", "max", "st
 def matmul_multi_reduce(adj, B: torch.Tensor, reduces=("mean", "min", "max", "std"), eps: float = 1e-5, fused: bool = True):
     """``spmm_multi_reduce`` on the structure of a SparseTensor or a ``backend_pim`` wrapper (its stored values are not used: unit weights)"""
     return spmm_multi_reduce(EdgeGraph.of(adj), B, reduces, eps, fused=fused)
+
+
+# ---- softmax aggregation per feature in one gather ----
+def _run_spmm_softmax(g: EdgeGraph, X: torch.Tensor, tv: torch.Tensor, want_lse: bool):
+    """X [ncols, h] contiguous and tv [h] (compute dtype) on g.device -> (out [nrows, h] in X's dtype, lse [nrows, h] in the compute dtype or None)"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
+    h = X.size(1)
+    out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
+    lse = torch.empty((g.nrows, h), dtype=tv.dtype, device=g.device) if want_lse else None
+    if g.nrows == 0:
+        return out, lse
+    ws = _workspace(L.spmm_softmax_workspace(dt, g.nrows, g.nnz, h), g.device)
+    L.spmm_softmax(dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), tv.data_ptr(), h, out.data_ptr(), h,
+                   0 if lse is None else lse.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out, lse
+
+
+class SpmmSoftmax(torch.autograd.Function):
+    """forward: one pygim_spmm_softmax; backward: one pygim_spmm_softmax_backward on the transposed structure, which takes the
+    probabilities again from the saved log-sum-exp.  Saved: X, t, out and lse -- node-sized, nothing of size nnz."""
+
+    @staticmethod
+    def forward(ctx, g, X, tv):
+        grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        out, lse = _run_spmm_softmax(g, X, tv, grad)
+        ctx.g = g
+        if grad:
+            ctx.save_for_backward(X, tv, out, lse)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        g = ctx.g
+        X, tv, out, lse = ctx.saved_tensors
+        L, _ = _backend()
+        dt = _gather_code(X.dtype)
+        h = X.size(1)
+        G = G.to(X.dtype).contiguous()
+        gt, _ = g.transposed()
+        dX = torch.empty((g.ncols, h), dtype=X.dtype, device=g.device)
+        dT = torch.empty((g.ncols, h), dtype=tv.dtype, device=g.device) if ctx.needs_input_grad[2] else None
+        if g.ncols > 0:
+            ws = _workspace(L.spmm_softmax_backward_workspace(dt, g.ncols, g.nnz, h), g.device)
+            L.spmm_softmax_backward(dt, g.ncols, gt.rowptr.data_ptr(), gt.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), tv.data_ptr(), h, G.data_ptr(), h,
+                                    out.data_ptr(), h, lse.data_ptr(), dX.data_ptr(), h, 0 if dT is None else dT.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream(g.device))
+        return None, (dX if ctx.needs_input_grad[1] else None), (None if dT is None else dT.sum(0))
+
+
+def _softmax_composed(g: EdgeGraph, X: torch.Tensor, tv: torch.Tensor):
+    """the same aggregation from functions that exist: X[col], edge_softmax with heads = h, spmm_values with heads = h.  It holds
+    several [nnz, h] tensors: the CPU-checkable and small-graph reference of the fused call.  16-bit X is taken up to float32 and the result
+    rounded once."""
+    from .attention import edge_softmax, spmm_values
+
+    Xc = X.to(tv.dtype)
+    p = edge_softmax(g, Xc.index_select(0, g.col.long()) * tv)
+    return spmm_values(g, p, Xc, heads=X.size(1)).to(X.dtype)
+
+
+def spmm_softmax(graph, X: torch.Tensor, t=1.0, fused: bool = True):
+    """``out[r, f] = sum over the stored entries e of row r of softmax_e(t[f] * X[col[e], f]) * X[col[e], f]``: PyG's
+    ``SoftmaxAggregation`` (``aggr="softmax"``, GENConv / DeeperGCN), a softmax per (row, feature) with the feature itself as the score
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; X [columns, h] in float32, float64, bfloat16 or float16 (16-bit:
+    float32 arithmetic, the result rounded once); t: the temperature, a float, a 0-d tensor or an ``[h]`` tensor (``t = 0``: the mean;
+    large ``t``: towards the max), taken to the compute dtype on the device.  Unit weights; duplicates count separately; empty rows
+    give 0.  Differentiable in X and in t (one backward gather on the transposed structure, nothing of size nnz is kept or allocated);
+    no double backward.  ``fused=False`` composes the same result from ``edge_softmax`` and ``spmm_values`` with ``heads = h`` and
+    holds ``[nnz, h]`` tensors.  Runs on the device; CPU tensors are staged there and the result comes back to X's device."""
+    if X.dtype not in FLOAT_TYPES and X.dtype not in HALF_TYPES:
+        raise TypeError(f"spmm_softmax: X must be float32, float64, bfloat16 or float16, got {X.dtype}")
+    g = EdgeGraph.of(graph)
+    if X.dim() != 2 or X.size(0) != g.ncols or X.size(1) < 1:
+        raise ValueError(f"spmm_softmax: X must be [{g.ncols}, h], got {tuple(X.shape)}")
+    h = X.size(1)
+    ct = _compute_dtype(X.dtype)
+    if torch.is_tensor(t):
+        if not t.is_floating_point():
+            raise TypeError(f"spmm_softmax: t must be a float or a floating-point tensor, got {t.dtype}")
+        if t.dim() > 1 or (t.dim() == 1 and t.size(0) != h):
+            raise ValueError(f"spmm_softmax: t must be a scalar or [{h}], got {tuple(t.shape)}")
+        tv = t.to(g.device, ct).expand(h).contiguous()   # autograd takes the gradient back to t's shape and dtype
+    else:
+        tv = torch.full((h,), float(t), dtype=ct, device=g.device)
+    home = X.device
+    Xd = X.to(g.device).contiguous()
+    if not fused:
+        return _softmax_composed(g, Xd, tv).to(home)
+    return SpmmSoftmax.apply(g, Xd, tv).to(home)
+
+
+def matmul_softmax(adj, B: torch.Tensor, t=1.0, fused: bool = True):
+    """``spmm_softmax`` on the structure of a SparseTensor or a ``backend_pim`` wrapper (its stored values are not used: unit weights)"""
+    if getattr(adj, "row_sharded", False):
+        raise NotImplementedError("matmul_softmax is not available on a RowShardAdj (one GPU only)")
+    return spmm_softmax(EdgeGraph.of(adj), B, t, fused=fused)

@@ -13,7 +13,15 @@ process, written to profiles/exp_multi_reduce.txt (--out) as JSON lines:
   the fused=False composition of the last (one spmm_reduce per statistic, two for std);
   forward + backward of the four-statistic call, fused against composed, with the peak of allocated memory;
   the bytes pygim_spmm_multi_reduce_workspace returns.
-    python scripts/exp_reduce.py --section multi [--iters 10] [--out profiles/exp_multi_reduce.txt]"""
+    python scripts/exp_reduce.py --section multi [--iters 10] [--out profiles/exp_multi_reduce.txt]
+--section softmax: softmax aggregation per feature in one gather (pygim_spmm_softmax and its backward), float32 and bfloat16, two rounds
+in one process, written to profiles/exp_softmax.txt (--out) as JSON lines:
+  on the Reddit-shaped graph spmm_values with one head and unit weights (the yardstick), the fused forward with and without lse, and
+    forward + backward (one backward gather on the transposed structure) with t requiring a gradient, with the peak of allocated memory;
+  on products-mini the same beside the fused=False composition (X[col], edge_softmax and spmm_values with heads = h: it fits there),
+    forward and forward + backward, with peak memory;
+  the bytes the two workspace functions return.
+    python scripts/exp_reduce.py --section softmax [--iters 10] [--out profiles/exp_softmax.txt]"""
 import argparse
 import json
 import os
@@ -108,16 +116,92 @@ def section_multi(args):
     torch.ops.pim_ops.dpu_release()
 
 
+def section_softmax(args):
+    dev = torch.device("cuda", 0)
+    h, iters = args.h, args.iters
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    out_path = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exp_softmax.txt")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    sink = open(out_path, "w")
+
+    def peak(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        ms = timed(fn, reps)
+        return ms, (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20
+
+    for shape, composed in (("reddit", False), ("products-mini", True)):
+        n, nnz, d_max = synth.SHAPES[shape]
+        rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+        g = attention.EdgeGraph(rowptr, col, (n, n))
+        g.transposed()   # built once, outside the timings
+
+        def line(**kw):
+            text = json.dumps({"graph": shape, "h": h, "nnz": nnz, **kw})
+            print(text, flush=True)
+            sink.write(text + "\n")
+            sink.flush()
+
+        ones = torch.ones(nnz, 1, device=dev)
+        for dtype, name, code in ((torch.float32, "float32", _lib.FLT32), (torch.bfloat16, "bfloat16", _lib.BF16)):
+            x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform").to(dtype)
+            G = synth.features(n, h, torch.float32, seed=1, device=dev, kind="uniform").to(dtype)
+            tv = torch.linspace(0.5, 2.0, h, device=dev)
+            gathered = nnz * h * x.element_size()
+
+            def step(fused):
+                xx, tt = x.detach().requires_grad_(), tv.detach().requires_grad_()
+                red.spmm_softmax(g, xx, tt, fused=fused).backward(G)
+                return xx.grad, tt.grad
+
+            for rnd in range(2):
+                t = {"spmm_values_heads1": timed(lambda: attention._run_spmm_values(g, ones, x, 1), iters),
+                     "softmax": timed(lambda: red._run_spmm_softmax(g, x, tv, False), iters),
+                     "softmax_lse": timed(lambda: red._run_spmm_softmax(g, x, tv, True), iters)}
+                fb_ms, fb_mib = peak(lambda: step(True), max(iters // 2, 1))
+                sv = t["spmm_values_heads1"]
+                extra = {}
+                if composed:
+                    with torch.no_grad():
+                        c_ms, c_mib = peak(lambda: red.spmm_softmax(g, x, tv, fused=False), max(iters // 2, 1))
+                    cfb_ms, cfb_mib = peak(lambda: step(False), 1)   # its spmm_values gradient is one sddmm per head: h launches
+                    extra = dict(composed_forward_ms=round(c_ms, 3), composed_forward_peak_mib=round(c_mib, 1),
+                                 composed_forward_over_fused=round(c_ms / t["softmax"], 2), composed_fwd_bwd_ms=round(cfb_ms, 3),
+                                 composed_fwd_bwd_peak_mib=round(cfb_mib, 1), composed_fwd_bwd_over_fused=round(cfb_ms / fb_ms, 2))
+                line(dtype=name, round=rnd, **{k + "_ms": round(v, 3) for k, v in t.items()},
+                     softmax_over_values=round(t["softmax"] / sv, 3), softmax_lse_over_values=round(t["softmax_lse"] / sv, 3),
+                     softmax_gather_tb_s=round(gathered / t["softmax"] / 1e9, 2), fwd_bwd_ms=round(fb_ms, 3), fwd_bwd_peak_mib=round(fb_mib, 1),
+                     fwd_bwd_over_values=round(fb_ms / sv, 3), backward_over_values=round((fb_ms - t["softmax_lse"]) / sv, 3), **extra)
+            if composed:
+                (dx_f, dt_f), (dx_c, dt_c) = step(True), step(False)
+                line(what="gradient check", dtype=name, dx_max_abs_fused_minus_composed=float((dx_f.float() - dx_c.float()).abs().max()),
+                     dx_max_abs=float(dx_c.float().abs().max()), dt_max_abs_fused_minus_composed=float((dt_f - dt_c).abs().max()),
+                     dt_max_abs=float(dt_c.abs().max()))
+                del dx_f, dx_c
+            line(what="workspace bytes", dtype=name, forward=_lib.spmm_softmax_workspace(code, n, nnz, h),
+                 backward=_lib.spmm_softmax_backward_workspace(code, n, nnz, h), spmm_values=_lib.spmm_values_workspace(code, n, nnz, h, 1))
+            del x, G
+        del g, ones, rowptr, col
+        torch.cuda.empty_cache()
+    sink.close()
+    torch.ops.pim_ops.dpu_release()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="reduce", choices=("reduce", "multi"))
-    ap.add_argument("--out", default=None, help="--section multi: where the JSON lines go (default profiles/exp_multi_reduce.txt)")
+    ap.add_argument("--section", default="reduce", choices=("reduce", "multi", "softmax"))
+    ap.add_argument("--out", default=None, help="--section multi / softmax: where the JSON lines go (default profiles/exp_multi_reduce.txt / exp_softmax.txt)")
     args = ap.parse_args()
     if args.section == "multi":
         return section_multi(args)
+    if args.section == "softmax":
+        return section_softmax(args)
     dev = torch.device("cuda", 0)
     n, nnz, d_max = synth.SHAPES[args.shape]
     h, iters = args.h, args.iters
