@@ -61,7 +61,7 @@ typedef enum {
     PYGIM_FLT32 = 4,
     PYGIM_DBL64 = 5,
     /* 16-bit FEATURE types (IEEE binary16, bfloat16).  Valid only for pygim_sddmm, pygim_spmm_values, pygim_gat_aggregate,
-     * pygim_sparse_attention, pygim_gatv2_aggregate, pygim_gatv2_backward (and the *_dropout forms of these four), pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
+     * pygim_sparse_attention, pygim_gatv2_aggregate, pygim_gatv2_backward (and the *_dropout forms of these four, pygim_gat_aggregate_edge, pygim_sparse_attention_bias), pygim_spmm_reduce with PYGIM_REDUCE_MEAN and their *_workspace functions ("16-bit features" below); every other entry
      * point -- group creation, edge softmax, the max / min reductions and their backward, the quantisers -- rejects them like
      * an unknown type. */
     PYGIM_FLT16 = 6,
@@ -437,6 +437,40 @@ int pygim_gatv2_backward_dropout(int dtype, int transposed, int64_t nrows, const
 int pygim_attention_dropout_mask(int dtype, int64_t nnz, int64_t heads, const int32_t *entry_ids /* [nnz] or NULL */, double p,
                                  uint64_t seed, void *mask /* [nnz, heads] */, void *stream);
 int pygim_attention_dropout_host(int64_t nnz, int64_t heads, int64_t e0, double p, uint64_t seed, uint8_t *keep /* [nnz, heads] */);
+
+/* ---- edge terms: one scalar per (stored entry, head) inside the score of the fused attention kernels ----
+ * The edge features of PyG's GATConv(edge_dim=), the learned attention bias of graph transformers, and additive masks.  The term is
+ * [nnz, heads], contiguous, in the stored order of A (entry e of the CSR, the index the dropout hash takes), read inside the gather
+ * beside the gathered row; nothing else of size nnz is read or written.
+ *   pygim_gat_aggregate_edge:    z[e, k] = a_dst[r, k] + a_src[colind[e], k] + a_edge[e, k],  s = z >= 0 ? z : negative_slope * z
+ *     (the term is added BEFORE the leaky ReLU), then the softmax and product of pygim_gat_aggregate.
+ *   pygim_sparse_attention_bias: s[e, k] = scale * sum_{f in head k} Q[r, f] * K[colind[e], f] + bias[e, k]
+ *     (the term is added after the scaling), then the softmax and product of pygim_sparse_attention.
+ * The signatures are those of the *_dropout forms with the term inserted before (p, seed).  The term's type is the compute type:
+ * FLT32 / DBL64 = the feature type, FLT32 beside FLT16 / BF16 features.  Everything of the base contract holds: device pointers,
+ * strides, nnz = 0 (the term may then be NULL), empty rows, lse optional, bounds, determinism (no atomics, the same bits on every
+ * launch), the launch shape (pygim_gather_launch_shape of the base kind); the EXISTING workspace functions serve them
+ * (pygim_gat_aggregate_workspace, pygim_sparse_attention_workspace).  Dropout is that of the *_dropout forms: p = 0 runs the
+ * instantiation without dropout and does not read seed.
+ *   PYGIM_ERR_INVALID, answered before any launch: a NULL term with nnz > 0; p < 0, p >= 1 or NaN; everything the base call rejects
+ *     (heads not dividing h, a head wider than 256 features for sparse attention, bad sizes, strides, pointers or workspace).
+ *   A term of -inf masks its (entry, head) exactly as a -inf node term does: probability 0 wherever it stands; a (row, head) with no
+ *     other entries stores NaN and lse = -inf.
+ *   A term of +inf or NaN makes that row and head NaN and nothing else.
+ *   A term of exactly 0 everywhere stores the bits of the base call (of the *_dropout call for p > 0): z + 0 and scale * s + 0 are exact.
+ * Not covered: feature-wide ([nnz, h]) edge embeddings -- key_j + e / value_j + e of PyG's TransformerConv(edge_dim), e inside the
+ * per-feature leaky ReLU of GATv2Conv(edge_dim); multi-GPU; a fused backward (the gradient of the term is the ds [nnz, heads] the
+ * composed backwards already form); heads wider than 256 features in the fused sparse-attention kernel. */
+int pygim_gat_aggregate_edge(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                             const void *a_dst, const void *a_src, int64_t heads, double negative_slope, const void *X,
+                             int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse, void *workspace,
+                             int64_t workspace_bytes, void *stream, const void *a_edge /* [nnz, heads] */, double p,
+                             uint64_t seed);
+int pygim_sparse_attention_bias(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                                const void *Q, int64_t ldq, const void *K, int64_t ldk, const void *V, int64_t ldv,
+                                int64_t h, int64_t heads, double scale, void *out, int64_t ldo, void *lse,
+                                void *workspace, int64_t workspace_bytes, void *stream, const void *bias /* [nnz, heads] */,
+                                double p, uint64_t seed);
 
 /* ---- reductions other than the sum over a row's stored entries (mean / max aggregation of GraphSAGE, PNA, GIN variants) ----
  *   pygim_spmm_reduce:  out[r, f] = REDUCE over the stored entries e of row r of w[e] * X[colind[e], f],  w[e] = values[e], or 1

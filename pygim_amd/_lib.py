@@ -29,6 +29,7 @@ EXPORTS = [
     "pygim_spmm_softmax", "pygim_spmm_softmax_workspace", "pygim_spmm_softmax_backward", "pygim_spmm_softmax_backward_workspace",
     "pygim_gat_aggregate_dropout", "pygim_sparse_attention_dropout", "pygim_gatv2_aggregate_dropout", "pygim_gatv2_backward_dropout",
     "pygim_attention_dropout_mask", "pygim_attention_dropout_host",
+    "pygim_gat_aggregate_edge", "pygim_sparse_attention_bias",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -107,6 +108,9 @@ def lib():
         L.pygim_gatv2_backward_dropout.argtypes = list(L.pygim_gatv2_backward.argtypes) + [vp, c_dbl, c_u64]
         L.pygim_attention_dropout_mask.argtypes = [c_int, c_i64, c_i64, vp, c_dbl, c_u64, vp, vp]
         L.pygim_attention_dropout_host.argtypes = [c_i64, c_i64, c_i64, c_dbl, c_u64, vp]
+        # edge terms: the base signature, then the term [nnz, heads], p, seed
+        L.pygim_gat_aggregate_edge.argtypes = list(L.pygim_gat_aggregate.argtypes) + [vp, c_dbl, c_u64]
+        L.pygim_sparse_attention_bias.argtypes = list(L.pygim_sparse_attention.argtypes) + [vp, c_dbl, c_u64]
         L.pygim_spmm_reduce.argtypes = [c_int, c_int, c_i64, vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
         L.pygim_spmm_reduce_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_reduce_workspace.restype = c_i64
@@ -398,6 +402,24 @@ def attention_dropout_host(nnz, heads, e0, p, seed):
     keep = np.empty((int(nnz), int(heads)), dtype=np.uint8)
     check(lib().pygim_attention_dropout_host(int(nnz), int(heads), int(e0), float(p), _seed(seed), keep.ctypes.data if keep.size else None))
     return keep
+
+
+# ---- edge terms (include/pygim_hip.h): the *_dropout calls with one scalar per (stored entry, head) inside the score; the term is
+# [nnz, heads] in the compute type, in the stored order of A.  The base entry points' *_workspace functions serve them.
+def gat_aggregate_edge(dtype, nrows, rowptr_ptr, col_ptr, nnz, a_dst_ptr, a_src_ptr, heads, negative_slope, x_ptr, ldx, h, out_ptr, ldo, lse_ptr,
+                       ws_ptr, ws_bytes, stream, a_edge_ptr, p=0.0, seed=0):
+    """gat_aggregate with the score leaky_relu(a_dst[row] + a_src[col] + a_edge[entry]); p > 0: with attention dropout (p, seed)"""
+    check(lib().pygim_gat_aggregate_edge(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(a_dst_ptr), _vp(a_src_ptr),
+                                         int(heads), float(negative_slope), _vp(x_ptr), int(ldx), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr),
+                                         _vp(ws_ptr), int(ws_bytes), _vp(stream), _vp(a_edge_ptr), float(p), _seed(seed)))
+
+
+def sparse_attention_bias(dtype, nrows, rowptr_ptr, col_ptr, nnz, q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, h, heads, scale, out_ptr, ldo, lse_ptr,
+                          ws_ptr, ws_bytes, stream, bias_ptr, p=0.0, seed=0):
+    """sparse_attention with the score scale * Q[row] . K[col] + bias[entry]; p > 0: with attention dropout (p, seed)"""
+    check(lib().pygim_sparse_attention_bias(int(dtype), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(q_ptr), int(ldq), _vp(k_ptr),
+                                            int(ldk), _vp(v_ptr), int(ldv), int(h), int(heads), float(scale), _vp(out_ptr), int(ldo),
+                                            _vp(lse_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream), _vp(bias_ptr), float(p), _seed(seed)))
 
 
 def spmm_reduce_workspace(dtype, op, nrows, nnz, h):

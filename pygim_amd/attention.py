@@ -39,10 +39,19 @@ CPU generator (``torch.manual_seed`` reproduces a run) and the backward reuses i
 the argument launches.  Not covered by attention dropout: a captured graph replays the seed it was captured with; multi-GPU; heads wider
 than 256 features get it through the unfused composition only.
 
+Edge terms: ``gat_aggregate(..., a_edge=)`` and ``sparse_attention(..., bias=)`` take one scalar per stored entry and head, ``[nnz, heads]`` in
+the stored order of the graph (``g.row``, ``g.col``), inside the score: ``leaky_relu(a_dst[row] + a_src[col] + a_edge[e])`` -- the edge features of
+PyG's ``GATConv(edge_dim=)``, reduced to ``(lin_edge(edge_attr).view(-1, H, C) * att_edge).sum(-1)`` -- and ``scale * Q[row] . K[col] + bias[e]``, the
+learned attention bias of graph transformers.  A term of ``-inf`` is a mask: probability 0, gradient 0.  The kernels read the term at the entry's
+index beside the gathered row (pygim_gat_aggregate_edge, pygim_sparse_attention_bias: ``heads / h`` of the gathered bytes); the forward saves it
+as the input it is and creates nothing of size nnz; the composed backwards add it when they recompute the probabilities and return its gradient, the
+``ds`` they form anyway (after the leaky-ReLU factor for GAT, before the factor ``scale`` for the bias).  It combines with attention dropout; its dtype
+is that of the node terms (the compute dtype, or the features' 16-bit dtype, which is upcast).  ``None`` calls exactly what the call without it calls.
+
 Not covered: integer types, ``RowShardAdj`` / multi-GPU, double backward, capturing the backward into a graph, 16-bit device groups
-(``mul``), 16-bit ``edge_softmax`` and 16-bit max / min; for ``sparse_attention`` also a fused backward kernel, edge features / ``beta``
-of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass composition); for
-``gatv2_aggregate`` edge features, ``fill_value`` / self loops, and heads wider than 256 features when fused.
+(``mul``), 16-bit ``edge_softmax`` and 16-bit max / min; for ``sparse_attention`` also a fused backward kernel, the feature-wide edge embeddings
+(``key_j + e``, ``value_j + e``) / ``beta`` of PyG's TransformerConv, and heads wider than 256 features in the fused kernel (they run as the three-pass
+composition); for ``gatv2_aggregate`` edge features, ``fill_value`` / self loops, and heads wider than 256 features when fused.
 """
 from __future__ import annotations
 
@@ -176,6 +185,22 @@ def _dropout_seed(seed) -> int:
         return int(seed) & 0xFFFFFFFFFFFFFFFF
     lo, hi = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64).tolist()
     return (hi << 32) | lo
+
+
+def _edge_term(name: str, arg: str, t, g: "EdgeGraph", heads: int, feat_dtype) -> torch.Tensor:
+    """the per-entry term of a score (``a_edge`` of gat_aggregate, ``bias`` of sparse_attention) checked and brought to [nnz, heads] in the
+    compute dtype, contiguous, on the graph's device"""
+    if not torch.is_tensor(t) or not t.is_floating_point():
+        raise TypeError(f"{name}: {arg} must be a floating-point tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    allowed = (torch.float32, feat_dtype) if feat_dtype in HALF_TYPES else (feat_dtype,)
+    if t.dtype not in allowed:
+        raise TypeError(f"{name}: {arg} must be {' or '.join(str(d) for d in allowed)} beside {feat_dtype} features, got {t.dtype}")
+    if t.dim() == 1 and heads == 1:
+        t = t.unsqueeze(1)
+    if t.dim() != 2 or t.size(0) != g.nnz or t.size(1) != heads:
+        raise ValueError(f"{name}: {arg} must be [{g.nnz}, {heads}]" + (f" or [{g.nnz}]" if heads == 1 else "") +
+                         f" (one row per stored entry, in the order of the graph's row / col), got {tuple(t.shape)}")
+    return t.to(g.device, _compute_dtype(feat_dtype)).contiguous()
 
 
 def dropout_mask(graph, heads: int, p: float, seed: int, dtype=torch.float32, transposed: bool = False) -> torch.Tensor:
@@ -314,9 +339,10 @@ def edge_softmax(graph, scores: torch.Tensor) -> torch.Tensor:
     return P.reshape(scores.shape).to(home)
 
 
-def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool, p: float = 0.0, seed: int = 0):
+def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, want_lse: bool, p: float = 0.0, seed: int = 0, a_edge=None):
     """a_dst [nrows, heads], a_src [ncols, heads] (float32 beside 16-bit X, else X's dtype), X [ncols, h] contiguous on g.device ->
-    (out [nrows, h] in X's dtype, lse [nrows, heads] in a_dst's or None)"""
+    (out [nrows, h] in X's dtype, lse [nrows, heads] in a_dst's or None).  a_edge: None, or the per-entry term [nnz, heads] in a_dst's
+    dtype, contiguous (pygim_gat_aggregate_edge)"""
     L, _ = _backend()
     dt = _gather_code(X.dtype)
     h = X.size(1)
@@ -327,7 +353,9 @@ def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, 
     ws = _workspace(L.gat_aggregate_workspace(dt, g.nrows, g.nnz, h, heads), g.device)
     args = (dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, a_dst.data_ptr(), a_src.data_ptr(), heads, slope,
             X.data_ptr(), X.stride(0), h, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(), _stream(g.device))
-    if p > 0.0:
+    if a_edge is not None:
+        L.gat_aggregate_edge(*args, a_edge.data_ptr(), p, seed)
+    elif p > 0.0:
         L.gat_aggregate_dropout(*args, p, seed)
     else:   # exactly the call without the argument
         L.gat_aggregate(*args)
@@ -336,19 +364,24 @@ def _run_gat_aggregate(g: EdgeGraph, a_dst, a_src, X, heads: int, slope: float, 
 
 class GatAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, a_dst, a_src, X, slope, p, seed):
+    def forward(ctx, g, a_dst, a_src, X, slope, p, seed, a_edge=None):
         heads = a_src.size(1)
-        need = any(ctx.needs_input_grad[1:4])
-        out, lse = _run_gat_aggregate(g, a_dst, a_src, X, heads, slope, need, p, seed)
+        need = any(ctx.needs_input_grad[1:4]) or (a_edge is not None and ctx.needs_input_grad[7])
+        out, lse = _run_gat_aggregate(g, a_dst, a_src, X, heads, slope, need, p, seed, a_edge)
         if need:
             ctx.g, ctx.heads, ctx.slope, ctx.p, ctx.seed = g, heads, slope, p, seed
-            ctx.save_for_backward(a_dst, a_src, X, out, lse)   # node-sized, all of them
+            if a_edge is None:
+                ctx.save_for_backward(a_dst, a_src, X, out, lse)   # node-sized, all of them
+            else:
+                ctx.save_for_backward(a_dst, a_src, X, out, lse, a_edge)   # and the term: an input of the call, nothing new of size nnz
         return out
 
     @staticmethod
     def backward(ctx, G):
         g, heads, slope = ctx.g, ctx.heads, ctx.slope
-        a_dst, a_src, X, out, lse = ctx.saved_tensors
+        a_dst, a_src, X, out, lse = ctx.saved_tensors[:5]
+        a_edge = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        want_edge = a_edge is not None and ctx.needs_input_grad[7]
         G = G.contiguous()
         h = X.size(1)
         hd = h // heads
@@ -357,6 +390,8 @@ class GatAggregate(torch.autograd.Function):
         # the probabilities again, from the node terms and the row's log-sum-exp: [nnz, heads], transient; in place where a tensor is done
         # with.  The peak is at dp.t().contiguous(): p, dp, ds and the byte mask neg, beside the int64 row / col / perm indices
         p = a_dst.index_select(0, row).add_(a_src.index_select(0, col))
+        if a_edge is not None:
+            p.add_(a_edge)   # the term of the entry, before the leaky ReLU as in the kernel; -inf gives p = 0 and ds = 0
         neg = p < 0
         torch.nn.functional.leaky_relu_(p, slope)
         p.sub_(lse.index_select(0, row)).exp_()
@@ -366,8 +401,8 @@ class GatAggregate(torch.autograd.Function):
             dX = _run_spmm_values(gt, (p if w is None else p * w).index_select(0, perm), G, heads)
         else:
             dX = None
-        da_dst = da_src = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+        da_dst = da_src = da_edge = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or want_edge:
             L, _ = _backend()
             es = X.element_size()
             ct = a_dst.dtype   # float32 beside 16-bit G, X and out: p, dp, delta and ds are never held in 16 bits
@@ -398,11 +433,13 @@ class GatAggregate(torch.autograd.Function):
                 da_dst = _run_spmm_values(g, ds, torch.ones((g.ncols, heads), dtype=ct, device=g.device), heads)
             if ctx.needs_input_grad[2]:   # column sums per head
                 da_src = _run_spmm_values(gt, ds.index_select(0, perm), torch.ones((g.nrows, heads), dtype=ct, device=g.device), heads)
-        return None, da_dst, da_src, dX, None, None, None
+            if want_edge:   # z is linear in the term: its gradient is ds itself
+                da_edge = ds
+        return None, da_dst, da_src, dX, None, None, None, da_edge
 
 
 def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tensor, negative_slope: float = 0.2, dropout: float = 0.0,
-                  seed=None) -> torch.Tensor:
+                  seed=None, a_edge=None) -> torch.Tensor:
     """the aggregation of a GAT layer, fused: with ``k = f // (h // heads)`` and e over the stored entries of row r
 
     ``out[r, f] = sum_e softmax_e(leaky_relu(a_dst[r, k] + a_src[col[e], k], negative_slope)) * X[col[e], f]``
@@ -419,7 +456,13 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
 
     ``dropout`` in [0, 1): attention dropout, PyG's ``GATConv(dropout=)`` -- every coefficient is dropped with that probability after the
     softmax, the kept ones are scaled by ``1 / (1 - dropout)``, inside the gather (see the module docstring).  ``seed``: 64 bits; ``None``
-    draws one per call from torch's default CPU generator.  0 is the call without the argument, bit for bit."""
+    draws one per call from torch's default CPU generator.  0 is the call without the argument, bit for bit.
+
+    ``a_edge``: a term per stored entry and head, ``[nnz, heads]`` (1-D: one head) in the stored order of the graph (``g.row``, ``g.col``):
+    the score becomes ``leaky_relu(a_dst[r, k] + a_src[col[e], k] + a_edge[e, k])`` -- the edge features of PyG's ``GATConv(edge_dim=)``
+    (``a_edge = (lin_edge(edge_attr).view(-1, H, C) * att_edge).sum(-1)``); ``-inf`` masks an (entry, head): probability 0, gradient 0.
+    Its dtype follows ``a_dst`` / ``a_src``.  Read inside the gather (pygim_gat_aggregate_edge); it is saved for the backward as the input
+    it is, and its gradient is the ``ds`` the backward forms anyway.  ``None`` is the call without the argument."""
     dropout = _dropout_rate("gat_aggregate", dropout)
     g = EdgeGraph.of(graph)
     if X.dtype in HALF_TYPES:
@@ -442,8 +485,12 @@ def gat_aggregate(graph, a_dst: torch.Tensor, a_src: torch.Tensor, X: torch.Tens
         raise ValueError(f"gat_aggregate: heads = {heads} must divide h = {X.size(1)}")
     home = X.device
     ct = _compute_dtype(X.dtype)
-    out = GatAggregate.apply(g, a_dst.to(g.device, ct).contiguous(), a_src.to(g.device, ct).contiguous(), X.to(g.device).contiguous(),
-                             float(negative_slope), dropout, _dropout_seed(seed) if dropout > 0.0 else 0)
+    operands = (g, a_dst.to(g.device, ct).contiguous(), a_src.to(g.device, ct).contiguous(), X.to(g.device).contiguous(),
+                float(negative_slope), dropout, _dropout_seed(seed) if dropout > 0.0 else 0)
+    if a_edge is None:
+        out = GatAggregate.apply(*operands)
+    else:
+        out = GatAggregate.apply(*operands, _edge_term("gat_aggregate", "a_edge", a_edge, g, heads, X.dtype))
     return out.to(home)
 
 
@@ -486,9 +533,9 @@ class HeadScores(torch.autograd.Function):
         return None, dQ, dK, None, None
 
 
-def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_lse: bool, p: float = 0.0, seed: int = 0):
+def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_lse: bool, p: float = 0.0, seed: int = 0, bias=None):
     """Q [nrows, h], K and V [ncols, h] contiguous on g.device, one dtype -> (out [nrows, h] in that dtype, lse [nrows, heads] in the
-    compute dtype or None)"""
+    compute dtype or None).  bias: None, or the per-entry term [nnz, heads] in the compute dtype, contiguous (pygim_sparse_attention_bias)"""
     L, _ = _backend()
     dt = _gather_code(Q.dtype)
     h = Q.size(1)
@@ -500,7 +547,9 @@ def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_
     args = (dt, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0),
             V.data_ptr(), V.stride(0), h, heads, scale, out.data_ptr(), h, lse.data_ptr() if want_lse else 0, ws.data_ptr(), ws.numel(),
             _stream(g.device))
-    if p > 0.0:
+    if bias is not None:
+        L.sparse_attention_bias(*args, bias.data_ptr(), p, seed)
+    elif p > 0.0:
         L.sparse_attention_dropout(*args, p, seed)
     else:
         L.sparse_attention(*args)
@@ -509,29 +558,37 @@ def _run_sparse_attention(g: EdgeGraph, Q, K, V, heads: int, scale: float, want_
 
 class SparseAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g, Q, K, V, heads, scale, p, seed):
-        need = any(ctx.needs_input_grad[1:4])
-        out, lse = _run_sparse_attention(g, Q, K, V, heads, scale, need, p, seed)
+    def forward(ctx, g, Q, K, V, heads, scale, p, seed, bias=None):
+        need = any(ctx.needs_input_grad[1:4]) or (bias is not None and ctx.needs_input_grad[8])
+        out, lse = _run_sparse_attention(g, Q, K, V, heads, scale, need, p, seed, bias)
         if need:
             ctx.g, ctx.heads, ctx.scale, ctx.p, ctx.seed = g, heads, scale, p, seed
-            ctx.save_for_backward(Q, K, V, out, lse)   # node-sized, all of them
+            if bias is None:
+                ctx.save_for_backward(Q, K, V, out, lse)   # node-sized, all of them
+            else:
+                ctx.save_for_backward(Q, K, V, out, lse, bias)   # and the term: an input of the call, nothing new of size nnz
         return out
 
     @staticmethod
     def backward(ctx, G):
         g, heads, scale = ctx.g, ctx.heads, ctx.scale
-        Q, K, V, out, lse = ctx.saved_tensors
+        Q, K, V, out, lse = ctx.saved_tensors[:5]
+        bias = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        want_bias = bias is not None and ctx.needs_input_grad[8]
         G = G.contiguous()
         hd = Q.size(1) // heads
         row = g.row.long()
         gt, perm = g.transposed()
         # the probabilities again, from the scores and the row's log-sum-exp: [nnz, heads], transient, in the compute dtype
-        p = _head_dots(g, Q, K, heads).mul_(scale).sub_(lse.index_select(0, row)).exp_()
+        p = _head_dots(g, Q, K, heads).mul_(scale)
+        if bias is not None:
+            p.add_(bias)   # the term of the entry, after the scaling as in the kernel; -inf gives p = 0 and ds = 0
+        p.sub_(lse.index_select(0, row)).exp_()
         # attention dropout: w per (entry, head) again from the seed; dV gathers p * w, dP becomes w * G . v
         w = dropout_mask(g, heads, ctx.p, ctx.seed, p.dtype) if ctx.p > 0.0 else None
         dV = _run_spmm_values(gt, (p if w is None else p * w).index_select(0, perm), G, heads) if ctx.needs_input_grad[3] else None
-        dQ = dK = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+        dQ = dK = dbias = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or want_bias:
             ds = _head_dots(g, G, V, heads)   # dP
             if w is not None:
                 ds.mul_(w)
@@ -541,17 +598,21 @@ class SparseAttention(torch.autograd.Function):
                 delta = _run_spmm_values(g, p * ds, torch.ones((g.ncols, heads), dtype=p.dtype, device=g.device), heads)
             else:
                 delta = (G * out).view(g.nrows, heads, hd).sum(-1)   # = sum_e p * dp per (row, head), without a pass over the entries
-            ds.sub_(delta.index_select(0, row)).mul_(p).mul_(scale)   # dS = scale * P * (dP - delta[row])
+            ds.sub_(delta.index_select(0, row)).mul_(p)   # P * (dP - delta[row]): the gradient of the score, and of the term
             del p
+            if want_bias:
+                dbias = ds.clone() if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] else ds
+            if dbias is not ds:
+                ds.mul_(scale)   # dS = scale * P * (dP - delta[row])
             if ctx.needs_input_grad[1]:
                 dQ = _run_spmm_values(g, ds, K, heads)
             if ctx.needs_input_grad[2]:
                 dK = _run_spmm_values(gt, ds.index_select(0, perm), Q, heads)
-        return None, dQ, dK, dV, None, None, None, None
+        return None, dQ, dK, dV, None, None, None, None, dbias
 
 
 def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int = 1, scale=None, fused: bool = True, dropout: float = 0.0,
-                     seed=None) -> torch.Tensor:
+                     seed=None, bias=None) -> torch.Tensor:
     """scaled dot-product attention over the stored entries: with ``hd = h // heads``, ``k = f // hd`` and e over the entries of row r
 
     ``out[r, f] = sum_e softmax_e(scale * Q[r, head k] . K[col[e], head k]) * V[col[e], f]``
@@ -568,7 +629,14 @@ def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, h
 
     ``dropout`` in [0, 1), ``seed``: attention dropout as in :func:`gat_aggregate` (PyG's ``TransformerConv(dropout=)``).  With one seed
     ``fused=True`` and ``fused=False`` drop the same entries: the composition multiplies the ``edge_softmax`` result by
-    :func:`dropout_mask`."""
+    :func:`dropout_mask`.
+
+    ``bias``: a term per stored entry and head, ``[nnz, heads]`` (1-D: one head) in the stored order of the graph (``g.row``, ``g.col``):
+    the score becomes ``scale * Q[r, head k] . K[col[e], head k] + bias[e, k]`` -- the learned attention bias of graph transformers
+    (Graphormer, SAN, GPS); ``-inf`` masks an (entry, head): probability 0, gradient 0.  float32 / float64 like Q, float32 or Q's dtype beside
+    16-bit Q.  ``fused=True`` reads it inside the gather (pygim_sparse_attention_bias) and saves it as the input it is; its gradient is
+    ``P * (dP - delta[row])``, the gradient of the score before the factor ``scale``.  ``fused=False`` and wide heads add it to the composed
+    scores.  The feature-wide edge embeddings of PyG's ``TransformerConv(edge_dim=)`` are not covered.  ``None`` is the call without it."""
     dropout = _dropout_rate("sparse_attention", dropout)
     g = EdgeGraph.of(graph)
     heads = int(heads)
@@ -586,10 +654,16 @@ def sparse_attention(graph, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, h
     home = Q.device
     q, k, v = (t.to(g.device).contiguous() for t in (Q, K, V))
     seed = _dropout_seed(seed) if dropout > 0.0 else 0
+    if bias is not None:
+        bias = _edge_term("sparse_attention", "bias", bias, g, heads, Q.dtype)
     if fused and hd <= SA_MAX_HEAD:
-        out = SparseAttention.apply(g, q, k, v, heads, scale, dropout, seed)
+        if bias is None:
+            out = SparseAttention.apply(g, q, k, v, heads, scale, dropout, seed)
+        else:
+            out = SparseAttention.apply(g, q, k, v, heads, scale, dropout, seed, bias)
     else:
-        p = EdgeSoftmax.apply(g, HeadScores.apply(g, q, k, heads, scale), heads)
+        s = HeadScores.apply(g, q, k, heads, scale)
+        p = EdgeSoftmax.apply(g, s if bias is None else s + bias, heads)
         if dropout > 0.0:
             p = p * dropout_mask(g, heads, dropout, seed, p.dtype)
         out = SpmmValues.apply(g, p, v, heads)

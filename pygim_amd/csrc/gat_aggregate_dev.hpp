@@ -60,11 +60,15 @@ inline uint64_t gat_workspace_bytes(uint64_t nnz, uint64_t h, uint64_t heads, si
 // an X piece is widened as it is folded, acc / l is rounded once where a finished row is stored).
 // DROP: attention dropout (attn_dropout_dev.hpp).  A probability goes into l unchanged and into the accumulate as p * w, w = 1 / (1 - rate) or
 // 0 from the mask of (entry index base + kk, the piece's head hv[v]); m, l, lse and everything else are untouched.  dr is read only then.
-template <typename T, typename S, int VEC, int NV, bool WHOLE, bool DROP = false>
+// EDGE: a per-entry term of the score, z = a_dst + a_src + a_edge[e, k] before the leaky ReLU (the edge features of PyG's GATConv, an
+// additive mask).  a_edge is [nnz, heads] in the stored order of A and e = base + kk is the index the dropout hash takes: the 64 entries of
+// a batch are 64 * heads consecutive elements, each lane loads the one of its (entry, head) beside the gathered row.  Read only then.
+template <typename T, typename S, int VEC, int NV, bool WHOLE, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                     const T *__restrict__ a_dst, const T *__restrict__ a_src, uint32_t heads, T slope,
                                                     const S *__restrict__ X, uint64_t ldx, uint32_t h, uint32_t L, S *__restrict__ out, uint64_t ldo,
-                                                    T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr) {
+                                                    T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr,
+                                                    const T *__restrict__ a_edge = nullptr) {
     using V = typename SdVec<S, VEC>::type;
     constexpr int U = NV == 1 ? RG_U : RG_U / 2;
     if constexpr (WHOLE) L = 64;
@@ -158,6 +162,7 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
             for (uint32_t k0 = pos; k0 <= last; k0 += R * U) {
                 V x[U][NV];
                 T s[U][NV];
+                T ae[EDGE ? U : 1][NV];   // EDGE: the entry's term, loaded beside its row
                 bool ok[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
@@ -170,9 +175,11 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
                     for (int v = 0; v < NV; v++) {
                         x[u][v] = V(0);
                         s[u][v] = es_lowest<T>();   // an entry slot that is not in flight: never above M
+                        if constexpr (EDGE) ae[u][v] = T(0);
                         if (ok[u] && fok[v]) {
                             x[u][v] = *(const V *)(xr + f[v]);
                             s[u][v] = ar[hv[v]];
+                            if constexpr (EDGE) ae[u][v] = a_edge[(uint64_t)(base + kk) * heads + hv[v]];
                         }
                     }
                 }
@@ -182,7 +189,8 @@ __global__ __launch_bounds__(256) void k_gat_gather(const uint32_t *__restrict__
 #pragma unroll
                     for (int u = 0; u < U; u++) {
                         if (ok[u] && fok[v]) {
-                            const T z = ad[v] + s[u][v];
+                            T z = ad[v] + s[u][v];
+                            if constexpr (EDGE) z = z + ae[u][v];
                             s[u][v] = z >= T(0) ? z : slope * z;
                         }
                         M = s[u][v] > M ? s[u][v] : M;
@@ -258,22 +266,23 @@ __global__ __launch_bounds__(256) void k_gat_empty(const uint32_t *__restrict__ 
         for (uint32_t k = lane; k < heads; k += 64) lse[row * heads + k] = T(0);
 }
 
-template <typename T, typename S, int VEC, bool DROP>
+template <typename T, typename S, int VEC, bool DROP, bool EDGE>
 inline void launch_gat_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
                                 T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat, const LaunchShape &g,
-                                const AttnDrop<T> &dr, hipStream_t st) {
+                                const AttnDrop<T> &dr, const T *a_edge, hipStream_t st) {
     rg_dispatch(nnz, g, [&](auto nv, auto whole, dim3 grid, uint32_t L) {
-        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, decltype(nv)::value, decltype(whole)::value, DROP>), grid, dim3(256), 0, st, rowptr, colind, nrows, nnz, a_dst,
-                           a_src, heads, slope, X, ldx, h, L, out, ldo, lse, ws, ws_stat, dr);
+        hipLaunchKernelGGL((k_gat_gather<T, S, VEC, decltype(nv)::value, decltype(whole)::value, DROP, EDGE>), grid, dim3(256), 0, st, rowptr, colind, nrows, nnz,
+                           a_dst, a_src, heads, slope, X, ldx, h, L, out, ldo, lse, ws, ws_stat, dr, a_edge);
     });
 }
 
 // 16-byte pieces (of the storage type) under the conditions of launch_row_gather: aligned rows of X and out, and no piece across two heads
-// DROP: with attention dropout of (rate, seed) = dr; without it dr is not read
-template <typename T, typename S = T, bool DROP = false>
+// DROP: with attention dropout of (rate, seed) = dr; without it dr is not read.  EDGE: with the per-entry term a_edge [nnz, heads]; without it
+// a_edge is not read
+template <typename T, typename S = T, bool DROP = false, bool EDGE = false>
 inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const T *a_dst, const T *a_src, uint32_t heads,
                                  T slope, const S *X, uint64_t ldx, uint32_t h, S *out, uint64_t ldo, T *lse, void *workspace, hipStream_t st,
-                                 const AttnDrop<T> &dr = AttnDrop<T>()) {
+                                 const AttnDrop<T> &dr = AttnDrop<T>(), const T *a_edge = nullptr) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
@@ -281,8 +290,8 @@ inline void launch_gat_aggregate(const uint32_t *rowptr, const uint32_t *colind,
     T *ws_stat = (T *)((char *)workspace + gat_stat_offset(nnz, h, sizeof(T)));
     const bool aligned = ldx % V == 0 && ldo % V == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
     const LaunchShape g = row_gather_shape(h, h / heads, V, aligned);   // the walker's layout
-    if (g.vec > 1) launch_gat_gather_v<T, S, (int)V, DROP>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, st);
-    else launch_gat_gather_v<T, S, 1, DROP>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, st);
+    if (g.vec > 1) launch_gat_gather_v<T, S, (int)V, DROP, EDGE>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, a_edge, st);
+    else launch_gat_gather_v<T, S, 1, DROP, EDGE>(rowptr, colind, nrows, nnz, a_dst, a_src, heads, slope, X, ldx, h, out, ldo, lse, ws, ws_stat, g, dr, a_edge, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

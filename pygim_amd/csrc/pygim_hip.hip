@@ -716,22 +716,34 @@ int64_t pygim_gat_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int
 // attention dropout: the rate of the *_dropout entry points (0 <= p < 1; NaN fails the first comparison)
 static bool bad_dropout(double p) { return !(p >= 0.0 && p < 1.0); }
 
-// p = 0 launches the instantiation without dropout: the base entry point and its bits
+// p = 0 launches the instantiation without dropout: the base entry point and its bits.  edge: the call takes a per-entry term a_edge
+// [nnz, heads] (pygim_gat_aggregate_edge) and launches the EDGE instantiations
 static int gat_aggregate_call(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
                               int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse,
-                              void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+                              void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed, bool edge = false,
+                              const void *a_edge = nullptr) {
     if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: the dropout rate must lie in [0, 1)");
+    if (edge && nnz > 0 && !a_edge) return fail(PYGIM_ERR_INVALID, "gat_aggregate_edge: a_edge is NULL");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "gat_aggregate: heads must divide h");
     if (int rc = check_csr_call("gat_aggregate", "rowptr / colind / a_dst / a_src / X / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
-                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {a_dst, nnz > 0}, {a_src, nnz > 0}, {X, nnz > 0}},
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {a_dst, nnz > 0}, {a_src, nnz > 0}, {X, nnz > 0},
+                                 {a_edge, edge && nnz > 0}},
                                 pygim_gat_aggregate_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        if (p > 0.0)
+        if (edge && p > 0.0)
+            launch_gat_aggregate<T, S, true, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst,
+                                                   (const T *)a_src, (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out,
+                                                   (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, attn_dropout_args<T>(p, seed), (const T *)a_edge);
+        else if (edge)
+            launch_gat_aggregate<T, S, false, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst,
+                                                    (const T *)a_src, (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out,
+                                                    (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, AttnDrop<T>(), (const T *)a_edge);
+        else if (p > 0.0)
             launch_gat_aggregate<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const T *)a_dst,
                                              (const T *)a_src, (uint32_t)heads, (T)negative_slope, (const S *)X, (uint64_t)ldx, (uint32_t)h, (S *)out,
                                              (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, attn_dropout_args<T>(p, seed));
@@ -758,6 +770,13 @@ int pygim_gat_aggregate_dropout(int dtype, int64_t nrows, const int32_t *rowptr,
                               stream, p, seed);
 }
 
+int pygim_gat_aggregate_edge(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *a_dst, const void *a_src,
+                             int64_t heads, double negative_slope, const void *X, int64_t ldx, int64_t h, void *out, int64_t ldo, void *lse,
+                             void *workspace, int64_t workspace_bytes, void *stream, const void *a_edge, double p, uint64_t seed) {
+    return gat_aggregate_call(dtype, nrows, rowptr, colind, nnz, a_dst, a_src, heads, negative_slope, X, ldx, h, out, ldo, lse, workspace, workspace_bytes,
+                              stream, p, seed, true, a_edge);
+}
+
 int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {
     (void)nrows;
     if (!is_gather_type(dtype) || nnz < 0 || h < 1 || heads < 1 || h % heads != 0 || h / heads > (int64_t)SA_MAX_HEAD) return -1;
@@ -766,21 +785,34 @@ int64_t pygim_sparse_attention_workspace(int dtype, int64_t nrows, int64_t nnz, 
 
 static int sparse_attention_call(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq,
                                  const void *K, int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
-                                 void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
+                                 void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed, bool edge = false,
+                                 const void *bias = nullptr) {
     if (bad_dropout(p)) return fail(PYGIM_ERR_INVALID, "sparse_attention: the dropout rate must lie in [0, 1)");
+    if (edge && nnz > 0 && !bias) return fail(PYGIM_ERR_INVALID, "sparse_attention_bias: bias is NULL");
     if (int rc = need_init()) return rc;
     if (!is_gather_type(dtype)) return fail(PYGIM_ERR_INVALID, "sparse_attention: type must be FLT32, DBL64, FLT16 or BF16");
     if (h >= 1 && (heads < 1 || h % heads != 0)) return fail(PYGIM_ERR_INVALID, "sparse_attention: heads must divide h");
     if (h >= 1 && h / heads > (int64_t)SA_MAX_HEAD) return fail(PYGIM_ERR_INVALID, "sparse_attention: a head is at most 256 features wide");
     if (int rc = check_csr_call("sparse_attention", "rowptr / colind / Q / K / V / out", nrows, nnz, 0x7FFFFFFFll, h, 0x7FFFFFFFll, ldq < ldk ? ldq : ldk,
                                 ldv < ldo ? ldv : ldo,
-                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {Q, nnz > 0}, {K, nnz > 0}, {V, nnz > 0}},
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {Q, nnz > 0}, {K, nnz > 0}, {V, nnz > 0},
+                                 {bias, edge && nnz > 0}},
                                 pygim_sparse_attention_workspace(dtype, nrows, nnz, h, heads), workspace, workspace_bytes))
         return rc;
     with_gather_types(dtype, [&](auto t, auto s) {
         using T = decltype(t);
         using S = decltype(s);
-        if (p > 0.0)
+        if (edge && p > 0.0)
+            launch_sparse_attention<T, S, true, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q,
+                                                      (uint64_t)ldq, (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads,
+                                                      (T)scale, (S *)out, (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream,
+                                                      attn_dropout_args<T>(p, seed), (const T *)bias);
+        else if (edge)
+            launch_sparse_attention<T, S, false, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q,
+                                                       (uint64_t)ldq, (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads,
+                                                       (T)scale, (S *)out, (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, AttnDrop<T>(),
+                                                       (const T *)bias);
+        else if (p > 0.0)
             launch_sparse_attention<T, S, true>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)Q, (uint64_t)ldq,
                                                 (const S *)K, (uint64_t)ldk, (const S *)V, (uint64_t)ldv, (uint32_t)h, (uint32_t)heads, (T)scale, (S *)out,
                                                 (uint64_t)ldo, (T *)lse, workspace, (hipStream_t)stream, attn_dropout_args<T>(p, seed));
@@ -805,6 +837,13 @@ int pygim_sparse_attention_dropout(int dtype, int64_t nrows, const int32_t *rowp
                                    void *lse, void *workspace, int64_t workspace_bytes, void *stream, double p, uint64_t seed) {
     return sparse_attention_call(dtype, nrows, rowptr, colind, nnz, Q, ldq, K, ldk, V, ldv, h, heads, scale, out, ldo, lse, workspace, workspace_bytes, stream,
                                  p, seed);
+}
+
+int pygim_sparse_attention_bias(int dtype, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *Q, int64_t ldq,
+                                const void *K, int64_t ldk, const void *V, int64_t ldv, int64_t h, int64_t heads, double scale, void *out, int64_t ldo,
+                                void *lse, void *workspace, int64_t workspace_bytes, void *stream, const void *bias, double p, uint64_t seed) {
+    return sparse_attention_call(dtype, nrows, rowptr, colind, nnz, Q, ldq, K, ldk, V, ldv, h, heads, scale, out, ldo, lse, workspace, workspace_bytes, stream,
+                                 p, seed, true, bias);
 }
 
 int64_t pygim_gatv2_aggregate_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h, int64_t heads) {

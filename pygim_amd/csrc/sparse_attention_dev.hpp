@@ -39,11 +39,15 @@ constexpr uint32_t SA_MAX_HEAD = 256;   // features of one head: 64 lanes x 4 sc
 // head0: the first head of this launch (blockIdx.y counts chunks of L / LH heads from there).
 // DROP: attention dropout as in k_gat_gather -- pr into l unchanged, pr * w into the accumulate, w from (entry index base + kk, the lane's
 // head: head0 and the blockIdx.y chunk included, so the mask does not depend on the launch shape).
-template <typename T, typename S, int VEC, int NP, bool DROP = false>
+// EDGE: a per-entry bias of the score, s = scale * dot + a_edge[e, head] after the butterfly and the scaling, before the maximum (the attention
+// bias of graph transformers, an additive mask); a_edge is [nnz, heads] in the stored order of A, e = base + kk as for the dropout hash.  Every
+// lane of a head loads the same element, so the head's redundant (m, l) stay equal.  Read only then.
+template <typename T, typename S, int VEC, int NP, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t nnz,
                                                    const S *__restrict__ Q, uint64_t ldq, const S *__restrict__ K, uint64_t ldk, const S *__restrict__ Vm,
                                                    uint64_t ldv, uint32_t h, uint32_t heads, uint32_t head0, T scale, uint32_t LH, uint32_t L, S *__restrict__ out,
-                                                   uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr) {
+                                                   uint64_t ldo, T *__restrict__ lse, T *__restrict__ ws, T *__restrict__ ws_stat, AttnDrop<T> dr,
+                                                   const T *__restrict__ a_edge = nullptr) {
     using V = typename SdVec<S, VEC>::type;
     constexpr int U = RG_U / NP;
     const uint32_t R = 64 / L;
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
             for (uint32_t k0 = pos; k0 <= last; k0 += R * U) {
                 V kx[U][NP], vx[U][NP];
                 T s[U];
+                T ae[EDGE ? U : 1];   // EDGE: the entry's bias, loaded beside its rows
                 bool ok[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
@@ -147,6 +152,7 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
                     const uint32_t col = rg_take32<false>(my_col, ok[u] ? kk : pos);
                     const S *kr = K + (uint64_t)col * ldk;
                     const S *vr = Vm + (uint64_t)col * ldv;
+                    if constexpr (EDGE) ae[u] = ok[u] && hok ? a_edge[(uint64_t)(base + kk) * heads + head] : T(0);
 #pragma unroll
                     for (int p = 0; p < NP; p++) {
                         kx[u][p] = V(0);
@@ -171,7 +177,8 @@ __global__ __launch_bounds__(256) void k_sa_gather(const uint32_t *__restrict__ 
                 T M = m;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    s[u] = ok[u] ? scale * s[u] : es_lowest<T>();   // not in flight: never above M
+                    if constexpr (EDGE) s[u] = ok[u] ? scale * s[u] + ae[u] : es_lowest<T>();
+                    else s[u] = ok[u] ? scale * s[u] : es_lowest<T>();   // not in flight: never above M
                     M = s[u] > M ? s[u] : M;
                 }
                 const T c = m == M ? T(1) : es_exp(m - M);
@@ -224,15 +231,15 @@ inline LaunchShape head_gather_shape(uint32_t h, uint32_t heads, uint32_t V, boo
     return g;
 }
 
-template <typename T, typename S, int VEC, bool DROP>
+template <typename T, typename S, int VEC, bool DROP, bool EDGE>
 inline void launch_sa_gather_v(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Q, uint64_t ldq, const S *K, uint64_t ldk,
                                const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse, T *ws, T *ws_stat,
-                               const LaunchShape &g, const AttnDrop<T> &dr, hipStream_t st) {
+                               const LaunchShape &g, const AttnDrop<T> &dr, const T *a_edge, hipStream_t st) {
     const unsigned blocks = (unsigned)((row_gather_runs(nnz) + 3) / 4);
 #define PYGIM_SA_LAUNCH(NP)                                                                                                                                    \
     for (uint32_t c0 = 0; c0 < g.chunks; c0 += LS_MAX_CHUNKS)                                                                                                  \
-    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP, DROP>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st, rowptr,  \
-                       colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * g.per, scale, g.LH, g.L, out, ldo, lse, ws, ws_stat, dr)
+    hipLaunchKernelGGL((k_sa_gather<T, S, VEC, NP, DROP, EDGE>), dim3(blocks, g.chunks - c0 < LS_MAX_CHUNKS ? g.chunks - c0 : LS_MAX_CHUNKS), dim3(256), 0, st,   \
+                       rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, c0 * g.per, scale, g.LH, g.L, out, ldo, lse, ws, ws_stat, dr, a_edge)
     constexpr uint32_t MAX_NP = (SA_MAX_HEAD + VEC * 64 - 1) / (VEC * 64);   // only the piece counts a head of SA_MAX_HEAD can need
     if (g.npl == 1) PYGIM_SA_LAUNCH(1);
     if constexpr (MAX_NP >= 2)
@@ -243,11 +250,11 @@ inline void launch_sa_gather_v(const uint32_t *rowptr, const uint32_t *colind, u
 }
 
 // 16-byte pieces (of the storage type) when a head's features fill whole pieces and every row of Q, K, V and out starts 16-byte aligned;
-// else one element per lane.  The caller has checked h / heads <= SA_MAX_HEAD.
-template <typename T, typename S = T, bool DROP = false>
+// else one element per lane.  The caller has checked h / heads <= SA_MAX_HEAD.  EDGE: with the per-entry bias a_edge [nnz, heads].
+template <typename T, typename S = T, bool DROP = false, bool EDGE = false>
 inline void launch_sparse_attention(const uint32_t *rowptr, const uint32_t *colind, uint32_t nrows, uint32_t nnz, const S *Q, uint64_t ldq, const S *K,
                                     uint64_t ldk, const S *Vm, uint64_t ldv, uint32_t h, uint32_t heads, T scale, S *out, uint64_t ldo, T *lse,
-                                    void *workspace, hipStream_t st, const AttnDrop<T> &dr = AttnDrop<T>()) {
+                                    void *workspace, hipStream_t st, const AttnDrop<T> &dr = AttnDrop<T>(), const T *a_edge = nullptr) {
     constexpr uint32_t V = 16 / sizeof(S);
     if (nrows > 0) hipLaunchKernelGGL((k_gat_empty<T, S>), dim3((nrows + 3) / 4), dim3(256), 0, st, rowptr, nrows, h, heads, out, ldo, lse);
     if (nnz == 0) return;
@@ -256,8 +263,8 @@ inline void launch_sparse_attention(const uint32_t *rowptr, const uint32_t *coli
     const bool aligned = ldq % V == 0 && ldk % V == 0 && ldv % V == 0 && ldo % V == 0 && (uintptr_t)Q % 16 == 0 && (uintptr_t)K % 16 == 0 &&
                          (uintptr_t)Vm % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0;
     const LaunchShape g = head_gather_shape(h, heads, V, aligned);
-    if (g.vec > 1) launch_sa_gather_v<T, S, (int)V, DROP>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, st);
-    else launch_sa_gather_v<T, S, 1, DROP>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, st);
+    if (g.vec > 1) launch_sa_gather_v<T, S, (int)V, DROP, EDGE>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, a_edge, st);
+    else launch_sa_gather_v<T, S, 1, DROP, EDGE>(rowptr, colind, nrows, nnz, Q, ldq, K, ldk, Vm, ldv, h, heads, scale, out, ldo, lse, ws, ws_stat, g, dr, a_edge, st);
     const uint64_t runs = row_gather_runs(nnz);
     if (runs > 1)
         hipLaunchKernelGGL((k_gat_fixup<T, S>), dim3((unsigned)((runs + 2) / 4)), dim3(256), 0, st, rowptr, nrows, nnz, h, heads, ws, ws_stat, out, ldo, lse);

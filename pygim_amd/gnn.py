@@ -17,6 +17,8 @@ is ``spmm_values`` (values as an operand) instead of ``adj_t.mul`` (values froze
 bfloat16 / float16 features after ``model.to(torch.bfloat16)`` or under ``torch.autocast`` (so is ``SAGEConv(aggr="mean")``).
 ``GATConv(..., fused=True)`` / ``GAT(..., fused=True)`` aggregate with ``gat_aggregate`` instead: scores, softmax and product in one
 kernel, no ``[nnz, heads]`` tensor written or kept for the backward.  The default (``fused=False``) is the layer as before.
+``GATConv(..., edge_dim=d)`` takes PyG's edge features: ``forward(x, adj_t, edge_attr)`` with ``edge_attr`` [nnz, d] in the stored order of
+the adjacency; they enter the score as one scalar per entry and head, inside the fused kernel (``gat_aggregate(a_edge=)``) or on the composed scores.
 
 TransformerConv / GraphTransformer are the dot-product attention layer (PyG's TransformerConv without edge features or ``beta``) on
 ``pygim_amd.attention.sparse_attention``: one kernel per layer when ``fused`` is set, the three-pass composition otherwise; the same
@@ -94,9 +96,16 @@ class GATConv(torch.nn.Module):
     p = softmax of the scores over the entries of row i;  out[i] = sum_j p[(i, j)] * x'[j] per head; heads concatenated or averaged.
     ``fused=True``: everything after the two reductions ``a`` is one ``gat_aggregate`` call.
     ``dropout``: PyG's attention dropout on ``p`` (a fresh mask per forward while training, none in ``eval()``), inside the fused kernel
-    or on the ``edge_softmax`` result."""
+    or on the ``edge_softmax`` result.
+    ``edge_dim``: PyG's edge features.  ``forward(x, adj_t, edge_attr)`` takes ``edge_attr`` [nnz, edge_dim] in the stored order of the
+    adjacency (``EdgeGraph.of(adj_t).row`` / ``.col``: row-major CSR order) and adds ``a_edge = (lin_edge(edge_attr).view(-1, H, F) *
+    att_edge).sum(-1)`` to the score before the leaky ReLU.  ``a_edge`` is formed as ``edge_attr @ M`` with ``M[d, k] = sum_c
+    lin_edge.weight[k F + c, d] * att_edge[0, k, c]`` -- the same function of the same parameters without the [nnz, H F] tensor -- and goes
+    into ``gat_aggregate(a_edge=)`` (fused) or onto the composed scores.  Without ``edge_dim``, or with ``edge_attr=None``, the layer is
+    the one above."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused=False, dropout=0.0, **_):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused=False, dropout=0.0, edge_dim=None,
+                 **_):
         super().__init__()
         self.fused, self.dropout = bool(fused), _att_dropout("GATConv", dropout)
         self.heads, self.out_channels, self.concat, self.negative_slope = int(heads), int(out_channels), bool(concat), float(negative_slope)
@@ -107,8 +116,28 @@ class GATConv(torch.nn.Module):
         torch.nn.init.xavier_uniform_(self.lin.weight)
         torch.nn.init.xavier_uniform_(self.att_src)
         torch.nn.init.xavier_uniform_(self.att_dst)
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+        if self.edge_dim is not None:   # created last, so that the other parameters draw what they drew without edge_dim
+            if self.edge_dim < 1:
+                raise ValueError(f"GATConv: edge_dim must be at least 1, got {edge_dim}")
+            self.lin_edge = Linear(self.edge_dim, self.heads * self.out_channels, bias=False)
+            self.att_edge = torch.nn.Parameter(torch.empty(1, self.heads, self.out_channels))
+            torch.nn.init.xavier_uniform_(self.lin_edge.weight)
+            torch.nn.init.xavier_uniform_(self.att_edge)
 
-    def forward(self, x, adj_t):
+    def edge_term(self, edge_attr):
+        """``a_edge`` [nnz, heads] of ``edge_attr`` [nnz, edge_dim]: PyG's ``(lin_edge(edge_attr).view(-1, H, F) * att_edge).sum(-1)`` as one
+        [nnz, edge_dim] x [edge_dim, H] product"""
+        if self.edge_dim is None:
+            raise ValueError("GATConv: edge_attr was given, but the layer was built without edge_dim")
+        if edge_attr.dim() == 1 and self.edge_dim == 1:
+            edge_attr = edge_attr.unsqueeze(1)
+        if edge_attr.dim() != 2 or edge_attr.size(1) != self.edge_dim:
+            raise ValueError(f"GATConv: edge_attr must be [nnz, {self.edge_dim}], got {tuple(edge_attr.shape)}")
+        M = (self.lin_edge.weight.view(self.heads, self.out_channels, self.edge_dim) * self.att_edge.view(self.heads, self.out_channels, 1)).sum(1)
+        return F.linear(edge_attr, M)   # edge_attr @ M^T, M [H, edge_dim]; under autocast a 16-bit matmul
+
+    def forward(self, x, adj_t, edge_attr=None):
         from .attention import EdgeGraph, _dropout_seed, dropout_mask, edge_softmax, gat_aggregate, spmm_values
 
         g = EdgeGraph.of(adj_t)
@@ -117,11 +146,21 @@ class GATConv(torch.nn.Module):
         xp = self.lin(x).view(-1, H, F_)
         a_src = (xp * self.att_src).sum(-1)
         a_dst = (xp * self.att_dst).sum(-1)
+        a_edge = None
+        if edge_attr is not None:
+            if edge_attr.size(0) != g.nnz:
+                raise ValueError(f"GATConv: edge_attr must have one row per stored entry ({g.nnz}), got {tuple(edge_attr.shape)}")
+            a_edge = self.edge_term(edge_attr.to(x.device))
         if self.fused:
-            out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope, dropout=drop)
+            if a_edge is None:
+                out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope, dropout=drop)
+            else:   # beside 16-bit features (model.to(bfloat16), autocast) the term goes to float32, what the kernel reads
+                a_edge = a_edge.float() if xp.dtype in (torch.float16, torch.bfloat16) else a_edge.to(xp.dtype)
+                out = gat_aggregate(g, a_dst, a_src, xp.reshape(-1, H * F_), self.negative_slope, dropout=drop, a_edge=a_edge)
         else:
             row, col = g.row.long().to(x.device), g.col.long().to(x.device)
-            score = F.leaky_relu(a_dst.index_select(0, row) + a_src.index_select(0, col), self.negative_slope)
+            z = a_dst.index_select(0, row) + a_src.index_select(0, col)
+            score = F.leaky_relu(z if a_edge is None else z + a_edge.to(z.dtype), self.negative_slope)
             if score.dtype in (torch.float16, torch.bfloat16):   # edge_softmax is float32 / float64: 16-bit scores go up, and
                 score = score.float()                             # spmm_values takes the float32 probabilities beside 16-bit features
             p = edge_softmax(g, score)
@@ -138,7 +177,9 @@ class TransformerConv(torch.nn.Module):
     v = lin_value(x) as [N, H, F];  score of stored entry (i, j) = q[i] . k[j] / sqrt(F) per head;  p = softmax of the scores over the
     entries of row i;  out[i] = sum_j p[(i, j)] * v[j] per head; heads concatenated or averaged;  + lin_skip(x) with ``root_weight``.
     ``fused=True``: scores, softmax and product are one ``sparse_attention`` kernel (heads wider than 256 features run unfused).
-    ``dropout``: PyG's attention dropout on ``p``, active while training."""
+    ``dropout``: PyG's attention dropout on ``p``, active while training.
+    A per-entry, per-head attention bias or mask goes through ``pygim_amd.sparse_attention(bias=)`` directly; PyG's ``edge_dim`` here is the
+    feature-wide form (``key_j + e``, ``value_j + e``) and is not covered."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, root_weight=True, bias=True, fused=TRANSFORMER_FUSED_DEFAULT, dropout=0.0,
                  **_):
@@ -427,6 +468,9 @@ class GEN(_Stack):
 
 
 class GraphTransformer(_Stack):
+    """a stack of TransformerConv layers.  A learned per-edge, per-head attention bias (Graphormer, SAN, GPS) is ``pygim_amd.sparse_attention(bias=)``;
+    the layers here take no edge features."""
+
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=1, fused=TRANSFORMER_FUSED_DEFAULT,
                  att_dropout=0.0):
         assert hidden_channels % heads == 0, "GraphTransformer: heads must divide hidden_channels (the heads are concatenated)"

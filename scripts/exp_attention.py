@@ -28,7 +28,11 @@ warm-up.  JSON lines:
   attention dropout (--section dropout, on its own: profiles/exp_dropout.txt), heads = 1 and 8, FLT32 and BF16 (--dtypes), two rounds:
     forward, and forward + backward, of gat_aggregate, sparse_attention and gatv2_aggregate at p = 0 and p = 0.5, and -- with
     --parent-lib PATH, the parent commit's libpygim_hip.so loaded beside this build -- the parent's p = 0 calls between them.
-    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot|v2|dropout] [--forward-only] [--dtypes f32,bf16,f16]
+  edge terms (--section edge, on its own: profiles/exp_edge_term.txt), heads = 1 and 8, FLT32 and BF16 (--dtypes), two rounds: forward,
+    and forward + backward with torch.cuda.max_memory_allocated, of gat_aggregate and sparse_attention without a term, with a term
+    ([nnz, heads] float32, inside the gather) and as the fused=False composition with the same term; with --parent-lib PATH the parent
+    build's calls without a term between them.
+    python scripts/exp_attention.py [--iters 10] [--section all|base|fused|half|dot|v2|dropout|edge] [--forward-only] [--dtypes f32,bf16,f16]
   --section base runs everything but the fused part (the record in profiles/exp_attention.txt), --section fused that part alone
   (profiles/exp_gat_fused.txt); all = base + fused."""
 import argparse
@@ -503,13 +507,106 @@ def dropout_section(g, n, nnz, h, iters, dev, line, names, parent):
         del A, B, G
 
 
+def edge_section(g, n, nnz, h, iters, dev, line, names, parent):
+    """what a per-entry term of the score costs: gat_aggregate(a_edge=) and sparse_attention(bias=) next to the calls without a term (this
+    build and, with --parent-lib, the parent's, alternating) and next to the fused=False composition with the same term; forward, and
+    forward + backward with the peak of torch.cuda.max_memory_allocated over one step; heads = 1 and 8, two rounds"""
+    import torch.nn.functional as F
+
+    g.transposed()
+    slope = 0.2
+    a32, b32, g32 = (synth.features(n, h, torch.float32, seed=sd, device=dev, kind="uniform") for sd in (5, 6, 8))
+    nb = max(2, iters // 3)
+    row, col = g.row.long(), g.col.long()
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        return round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+
+    for name in names:
+        dt = HALF_DTYPES[name]
+        A, B, G = (t.to(dt) for t in (a32, b32, g32))
+        for heads in (1, 8):
+            hd = h // heads
+            gen = torch.Generator(device=dev).manual_seed(4)
+            a_dst = torch.randn(n, heads, device=dev, generator=gen) * 2
+            a_src = torch.randn(n, heads, device=dev, generator=gen) * 2
+            term = torch.rand(nnz, heads, device=dev, generator=gen) * 4 - 2
+
+            def gat_composed(a, b, x, e):   # the fused=False path of gnn.GATConv with the term on the scores
+                score = F.leaky_relu(a.index_select(0, row) + b.index_select(0, col) + e, slope)
+                return attention.spmm_values(g, attention.edge_softmax(g, score), x, heads)
+
+            calls = {
+                "gat_aggregate": (lambda e: attention._run_gat_aggregate(g, a_dst, a_src, B, heads, slope, False, 0.0, 0, e),
+                                  lambda t, e: attention.gat_aggregate(g, *t, slope, a_edge=e), gat_composed, (a_dst, a_src, B)),
+                "sparse_attention": (lambda e: attention._run_sparse_attention(g, A, B, B, heads, hd ** -0.5, False, 0.0, 0, e),
+                                     lambda t, e: attention.sparse_attention(g, *t, heads=heads, bias=e),
+                                     lambda q, k, v, e: attention.sparse_attention(g, q, k, v, heads=heads, fused=False, bias=e), (A, B, B)),
+            }
+            for fn_name, (fwd, full, composed, operands) in calls.items():
+                leaves = [t.clone().requires_grad_() for t in operands]
+                eterm = term.clone().requires_grad_()
+
+                def step(kind):
+                    for t in leaves + [eterm]:
+                        t.grad = None
+                    out = full(leaves, None) if kind == "none" else full(leaves, eterm) if kind == "term" else composed(*leaves, eterm)
+                    out.backward(G)
+
+                def fwd_composed():
+                    with torch.no_grad():
+                        return composed(*operands, term)
+
+                # one discarded pass per build, as in the dropout section, of the forward and of forward + backward: without the second the
+                # first forward + backward after a storage type's tensors are allocated came out 1.5 % slow once (profiles/exp_edge_term.txt)
+                timed(lambda: fwd(None), iters)
+                timed(lambda: step("none"), 1)
+                if parent is not None:
+                    with parent:
+                        timed(lambda: fwd(None), iters)
+                        timed(lambda: step("none"), 1)
+                for rnd in range(2):
+                    rec = dict(what=f"{fn_name} edge term", x_dtype=name, heads=heads, round=rnd)
+                    rec["fwd_none_ms"] = round(timed(lambda: fwd(None), iters), 3)
+                    if parent is not None:
+                        with parent:
+                            rec["fwd_parent_ms"] = round(timed(lambda: fwd(None), iters), 3)
+                    rec["fwd_term_ms"] = round(timed(lambda: fwd(term), iters), 3)
+                    rec["fwd_composed_ms"] = round(timed(fwd_composed, nb), 2)
+                    rec["fwdbwd_none_ms"] = round(timed(lambda: step("none"), nb), 2)
+                    if parent is not None:
+                        with parent:
+                            rec["fwdbwd_parent_ms"] = round(timed(lambda: step("none"), nb), 2)
+                    rec["fwdbwd_term_ms"] = round(timed(lambda: step("term"), nb), 2)
+                    rec["fwdbwd_composed_ms"] = round(timed(lambda: step("composed"), nb), 2)
+                    for kind in ("none", "term", "composed"):
+                        rec[f"fwdbwd_{kind}_peak_gib"] = peak(lambda: step(kind))
+                    rec["fwd_term_over_none"] = round(rec["fwd_term_ms"] / rec["fwd_none_ms"], 4)
+                    rec["fwd_composed_over_term"] = round(rec["fwd_composed_ms"] / rec["fwd_term_ms"], 3)
+                    rec["fwdbwd_composed_over_term"] = round(rec["fwdbwd_composed_ms"] / rec["fwdbwd_term_ms"], 3)
+                    if parent is not None:
+                        rec["fwd_none_over_parent"] = round(rec["fwd_none_ms"] / rec["fwd_parent_ms"], 4)
+                        rec["fwdbwd_none_over_parent"] = round(rec["fwdbwd_none_ms"] / rec["fwdbwd_parent_ms"], 4)
+                    line(**rec)
+                del leaves, eterm
+                for t in operands:
+                    t.grad = None
+                torch.cuda.empty_cache()
+            del term
+        del A, B, G
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot", "v2", "dropout"])
-    ap.add_argument("--parent-lib", default=None, help="--section dropout: the parent commit's libpygim_hip.so, timed alternately in the same run")
+    ap.add_argument("--section", default="all", choices=["all", "base", "fused", "half", "dot", "v2", "dropout", "edge"])
+    ap.add_argument("--parent-lib", default=None, help="--section dropout / edge: the parent commit's libpygim_hip.so, timed alternately in the same run")
     ap.add_argument("--small-shape", default="products-mini", help="--section v2: the graph on which fused=False fits in memory")
     ap.add_argument("--dtypes", default="f32,bf16,f16", help="--section half / dot: the storage types of the features to measure")
     ap.add_argument("--forward-only", action="store_true", help="skip (d) of the fused part: for a kernel trace of the forward kernels alone")
@@ -544,6 +641,10 @@ def main():
         del x
         dropout_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")],
                         OtherBuild(args.parent_lib) if args.parent_lib else None)
+    if args.section == "edge":
+        del x
+        edge_section(g, n, nnz, h, iters, dev, line, [k for k in args.dtypes.split(",") if k in ("f32", "bf16")],
+                     OtherBuild(args.parent_lib) if args.parent_lib else None)
     torch.ops.pim_ops.dpu_release()
 
 
