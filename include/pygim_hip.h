@@ -587,6 +587,69 @@ int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_
                                 const void *lse, void *dX, int64_t ldd, void *dT /* [ncols, h] contiguous or NULL */, void *workspace,
                                 int64_t workspace_bytes, void *stream);
 
+/* ---- feature-wide edge features in the message (GINEConv; GENConv / DeeperGCN with edge_dim) ----
+ * With E [nnz, h] (row stride lde) in stored CSR order -- the order of rowptr / colind, and of the a_edge term of pygim_gat_aggregate_edge --
+ *       msg[e, f] = act(X[colind[e], f] + E[e, f]) + eps        act: PYGIM_ACT_NONE (identity) or PYGIM_ACT_RELU; eps a finite or
+ *                                                               infinite number, taken to the compute type; unit weights, no values
+ *   pygim_spmm_edge:          out[r, f] = FOLD over the stored entries e of row r, in stored order, of msg[e, f]
+ *     op: PYGIM_REDUCE_SUM, _MEAN, _MAX or _MIN.  It is the kernel of pygim_spmm_values / pygim_spmm_reduce with one more operand: the wave
+ *     that owns 512 consecutive entries reads its 512 rows of E as one contiguous stream beside the gathered rows of X, and the fold, its
+ *     order (the scan, the xor tree of the lane groups, the runs in order), the slots, the fix-up and the tie rule of max / min (the
+ *     lowest entry index wins; arg [nrows, h] int32 or NULL, -1 for empty rows) are those of the fold without E.  With E = -0.0,
+ *     PYGIM_ACT_NONE and eps = 0 (which is not added) the message is X[colind[e], f] itself and out and arg have the BITS of
+ *     pygim_spmm_values with unit values (SUM) or pygim_spmm_reduce (MEAN, MAX, MIN).  Workspace: pygim_spmm_edge_workspace bytes (what
+ *     the fold without E needs), 16-byte aligned.
+ *   pygim_spmm_edge_softmax:  out[r, f] = sum_e softmax_e(t[f] * msg[e, f]) * msg[e, f], lse[r, f] = log sum_e exp(t[f] * msg[e, f])
+ *     pygim_spmm_softmax with msg in place of X[colind[e], f]: the same triple, fix-up, launch shape, workspace size, bounds (with x := msg)
+ *     and, for E = -0.0 / no activation / eps = 0, the same bits of out and lse.
+ *   pygim_spmm_edge_backward: the gradient with respect to E, one entry-order kernel, for G [nrows, ldg] and row r of entry e
+ *       dE[e, f] = act'(X[colind[e], f] + E[e, f]) * c[e, f]        act' = 1, or (x + e > 0) for relu
+ *       SUM: c = G[r, f]      MEAN: c = G[r, f] / (stored entries of row r)      MAX / MIN: c = G[r, f] if arg[r, f] == e, else 0
+ *       PYGIM_REDUCE_SOFTMAX: c = G[r, f] * p * (1 + t[f] * (msg - out[r, f])),  p = exp(t[f] * msg - lse[r, f])
+ *     (arg, or out and lse, are what the forward stored; pointers an op does not use are ignored).  The message is additive in X and E, so
+ *     the gradient of X is the sum of the dE rows per column: pygim_spmm_values on the CSR of A^T with the permutation as column ids,
+ *     unit values and X := dE -- no kernel of its own.  dT_part ([runs, h] contiguous in the compute type, runs =
+ *     pygim_spmm_edge_backward_workspace = ceil(nnz / 512); or NULL): run w stores the sum over its entries of G * p * msg * (msg - out),
+ *     per lane group in entry order, then the fixed xor tree; the gradient of t is the column sum, formed by the caller.  Every dE row has
+ *     one writer; no workspace, no atomics, the same bits on every launch; dE has the same bits with and without dT_part.
+ *     Known cost: SUM / MEAN with PYGIM_ACT_NONE is a broadcast of G[r] over the row's entries; it reads neither X nor E but still walks
+ *     colind and searches the rows like the other modes.
+ *   Contract (all three): that of pygim_spmm_softmax -- device pointers only, a valid CSR guaranteed by the caller, nnz = 0, nrows = 0,
+ *     empty rows (out 0, arg -1, lse -inf) and any h >= 1 allowed, every row stride >= h, work only enqueued on `stream`.
+ *   Types: FLT32, DBL64, FLT16, BF16 for SUM, MEAN and the softmax; FLT32 / DBL64 for MAX / MIN.  16-bit: X, E, G, out and dE are stored in
+ *     16 bits, widened as they are read (exact); eps, t, lse, dT_part, the slots and all arithmetic are float32; a value is rounded once,
+ *     where it is stored.
+ *   Non-finite inputs: the underlying fold applied to msg.  relu keeps NaN (NaN < 0 is false) and turns -inf into 0, so E = -inf under
+ *     relu gives msg = eps and a gradient of 0; a NaN or +-inf in E reaches only its own (row, feature).  MAX / MIN: a NaN message never
+ *     wins against a number; all-NaN rows store NaN and arg -1.
+ *   PYGIM_ERR_INVALID before any launch: E NULL with nnz > 0, an unknown op or act, NaN eps, a type the fold does not take (integers;
+ *     16-bit MAX / MIN), h > 65535 * 128, arg with SUM / MEAN, a row stride below h, a workspace that is too small or misaligned.
+ *   Measured (profiles/exp_edge_message.txt; Reddit-shaped graph at h = 32, products-mini at h = 256, two rounds; X stays in cache at
+ *     both, so the stream of E is the cost): the expectation was one gather plus one stream of nnz * h elements, about 2 x the plain
+ *     fold.  FLT32: the sum is 1.73 - 1.97 x pygim_spmm_values and reads E at 3.4 - 3.5 TB/s; the softmax is 1.61 x pygim_spmm_softmax on
+ *     products-mini but 2.12 x on the Reddit shape (E at 2.5 TB/s), SLOWER than expected: its arithmetic does not hide behind the
+ *     stream.  BF16: 1.57 - 1.75 x (sum) and 1.42 - 1.92 x (softmax), E at 1.4 - 2.9 TB/s: 16-bit storage does not halve the time.
+ *     Against the composition through [nnz, h] tensors: forward 5.9 - 33 x, forward + backward 4 - 35 x faster, at a peak of one dE above
+ *     the operands. */
+#define PYGIM_REDUCE_SUM 4
+#define PYGIM_REDUCE_SOFTMAX 5 /* pygim_spmm_edge_backward only */
+#define PYGIM_ACT_NONE 0
+#define PYGIM_ACT_RELU 1
+int64_t pygim_spmm_edge_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h);
+int pygim_spmm_edge(int dtype, int op, int act, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                    const void *X, int64_t ldx, const void *E, int64_t lde, int64_t h, void *out, int64_t ldo,
+                    int32_t *arg /* [nrows, h] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t pygim_spmm_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h);
+int pygim_spmm_edge_softmax(int dtype, int act, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz,
+                            const void *X, int64_t ldx, const void *E, int64_t lde, const void *t /* [h] device */, int64_t h, void *out,
+                            int64_t ldo, void *lse /* [nrows, h] contiguous or NULL */, void *workspace, int64_t workspace_bytes,
+                            void *stream);
+int64_t pygim_spmm_edge_backward_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h); /* runs: rows of dT_part */
+int pygim_spmm_edge_backward(int dtype, int op /* PYGIM_REDUCE_* incl. _SOFTMAX */, int act, double eps, int64_t nrows,
+                             const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X, int64_t ldx, const void *E,
+                             int64_t lde, const void *G, int64_t ldg, const int32_t *arg, const void *t, const void *out, int64_t ldo,
+                             const void *lse, int64_t h, void *dE, int64_t ldde, void *dT_part, void *stream);
+
 /* ---- which kernel instantiation and lane layout a call of the entry points above gets ----
  * The decision their launchers take, from the host functions the launchers themselves call: no device is touched and nothing is
  * launched (like the *_workspace functions it works without a GPU and without pygim_init_*).  `kind` names the entry point, `dtype`
@@ -594,7 +657,9 @@ int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_
  * workspace included) a multiple of 16 bytes.  heads is ignored by SDDMM, SPMM_REDUCE and SPMM_REDUCE_BACKWARD, h by EDGE_SOFTMAX;
  * SPMM_MULTI_REDUCE (FLT32, DBL64, FLT16, BF16: the lane layout of the mean fold, whatever the statistics) has no heads and takes
  * heads = 1 alone (anything else: PYGIM_ERR_INVALID); so do SPMM_SOFTMAX and SPMM_SOFTMAX_BACKWARD (the same types and the same lane
- * layout; `aligned` covers lse as well for the backward)
+ * layout; `aligned` covers lse as well for the backward), and SPMM_EDGE (pygim_spmm_edge and pygim_spmm_edge_softmax; `aligned` covers E and
+ * lde) and SPMM_EDGE_BACKWARD (`aligned` covers E, G, dE and, for the softmax, out and lse): the four gather types, the lane layout of
+ * SPMM_REDUCE and SPMM_SOFTMAX for the same numbers
  * (forward and backward are one kind: the backward only has one more pointer that must be aligned).
  *   out[0] vec       features per piece (per lane and load): 16 / element size, or 1
  *   out[1] pieces    pieces a lane holds at once: 1 or 2 (row walkers: SPMM_VALUES, SPMM_REDUCE, GAT_AGGREGATE, SPMM_REDUCE_BACKWARD,
@@ -628,6 +693,8 @@ int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_
 #define PYGIM_SHAPE_SPMM_MULTI_REDUCE 9
 #define PYGIM_SHAPE_SPMM_SOFTMAX 10
 #define PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD 11
+#define PYGIM_SHAPE_SPMM_EDGE 12
+#define PYGIM_SHAPE_SPMM_EDGE_BACKWARD 13
 #define PYGIM_SHAPE_PART_PIECE 1
 #define PYGIM_SHAPE_PART_CHUNK 2
 #define PYGIM_SHAPE_PART_HEADS 4

@@ -10,10 +10,10 @@ Layout:
   dist.py          sp_parts / ds_parts across the GPUs of one node (torch.distributed/RCCL)
   autograd.py      gradients of ``mul``: A^T . G through a transposed group, the edge values' SDDMM (``sddmm``)
   attention.py     products and softmax with per-call edge values (``EdgeGraph``, ``spmm_values``, ``edge_softmax``, the fused ``gat_aggregate``, ``sparse_attention`` and ``gatv2_aggregate``)
-  reduce.py        aggregation with a reduction other than the sum (``spmm_reduce``: mean / max / min, with gradients; ``spmm_multi_reduce``: several statistics in one gather; ``spmm_softmax``: softmax aggregation per feature in one gather)
+  reduce.py        aggregation with a reduction other than the sum (``spmm_reduce``: mean / max / min, with gradients; ``spmm_multi_reduce``: several statistics in one gather; ``spmm_softmax``: softmax aggregation per feature in one gather; ``spmm_edge``: messages with a feature-wide edge feature)
 """
 __version__ = "0.1.0"
 
 from .attention import EdgeGraph, dropout_mask, edge_softmax, gat_aggregate, gatv2_aggregate, sparse_attention, spmm_values  # noqa: E402,F401
 from .autograd import sddmm  # noqa: E402,F401
-from .reduce import matmul_softmax, spmm_multi_reduce, spmm_reduce, spmm_softmax  # noqa: E402,F401
+from .reduce import matmul_edge, matmul_softmax, spmm_edge, spmm_multi_reduce, spmm_reduce, spmm_softmax  # noqa: E402,F401

@@ -30,6 +30,8 @@ EXPORTS = [
     "pygim_gat_aggregate_dropout", "pygim_sparse_attention_dropout", "pygim_gatv2_aggregate_dropout", "pygim_gatv2_backward_dropout",
     "pygim_attention_dropout_mask", "pygim_attention_dropout_host",
     "pygim_gat_aggregate_edge", "pygim_sparse_attention_bias",
+    "pygim_spmm_edge", "pygim_spmm_edge_workspace", "pygim_spmm_edge_softmax", "pygim_spmm_edge_softmax_workspace",
+    "pygim_spmm_edge_backward", "pygim_spmm_edge_backward_workspace",
 ]
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSORTED = 0, 1, 2, 3, 4
@@ -37,10 +39,13 @@ INT8, INT16, INT32, INT64, FLT32, DBL64 = range(6)
 FLT16, BF16 = 6, 7   # 16-bit features: sddmm, spmm_values, gat_aggregate, sparse_attention, gatv2_* and spmm_reduce mean only (include/pygim_hip.h)
 CSR, COO = 0, 1
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 1, 2, 3
+REDUCE_SUM, REDUCE_SOFTMAX = 4, 5   # pygim_spmm_edge (SUM) and pygim_spmm_edge_backward (both)
+ACT_NONE, ACT_RELU = 0, 1           # the activation inside the message of pygim_spmm_edge*
 STAT_SUM, STAT_MEAN, STAT_MIN, STAT_MAX, STAT_VAR, STAT_STD = range(6)   # pygim_spmm_multi_reduce
 # pygim_gather_launch_shape: the kinds, the names of out[0..7] and the bits of "flags"
 (SHAPE_SPMM_VALUES, SHAPE_SPMM_REDUCE, SHAPE_GAT_AGGREGATE, SHAPE_SPARSE_ATTENTION, SHAPE_GATV2_AGGREGATE, SHAPE_GATV2_BACKWARD, SHAPE_SDDMM,
- SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD, SHAPE_SPMM_MULTI_REDUCE, SHAPE_SPMM_SOFTMAX, SHAPE_SPMM_SOFTMAX_BACKWARD) = range(12)
+ SHAPE_EDGE_SOFTMAX, SHAPE_SPMM_REDUCE_BACKWARD, SHAPE_SPMM_MULTI_REDUCE, SHAPE_SPMM_SOFTMAX, SHAPE_SPMM_SOFTMAX_BACKWARD, SHAPE_SPMM_EDGE,
+ SHAPE_SPMM_EDGE_BACKWARD) = range(14)
 SHAPE_FIELDS = ("vec", "pieces", "LH", "L", "per", "chunks", "launches", "flags")
 SHAPE_PART_PIECE, SHAPE_PART_CHUNK, SHAPE_PART_HEADS, SHAPE_SCALAR_SIZE, SHAPE_SCALAR_ALIGN = 1, 2, 4, 8, 16
 GATHER_MAX_H = 65535 * 128   # the widest row of spmm_values, spmm_reduce, spmm_multi_reduce, spmm_softmax, gat_aggregate and spmm_reduce_backward
@@ -126,6 +131,16 @@ def lib():
         L.pygim_spmm_softmax_backward_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
         L.pygim_spmm_softmax_backward_workspace.restype = c_i64
         L.pygim_spmm_softmax_backward.argtypes = [c_int, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_spmm_edge_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_edge_workspace.restype = c_i64
+        L.pygim_spmm_edge.argtypes = [c_int, c_int, c_int, ctypes.c_double, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_spmm_edge_softmax_workspace.argtypes = [c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_edge_softmax_workspace.restype = c_i64
+        L.pygim_spmm_edge_softmax.argtypes = [c_int, c_int, ctypes.c_double, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, vp]
+        L.pygim_spmm_edge_backward_workspace.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
+        L.pygim_spmm_edge_backward_workspace.restype = c_i64
+        L.pygim_spmm_edge_backward.argtypes = [c_int, c_int, c_int, ctypes.c_double, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, vp, c_i64,
+                                               vp, c_i64, vp, c_i64, vp, vp]
         L.pygim_group_free.argtypes = [c_i64]
         L.pygim_group_serial.argtypes = [c_i64, p_i64]
         L.pygim_spmm_run_group.argtypes = [c_i64, vp, vp, vp]
@@ -495,6 +510,53 @@ def spmm_softmax_backward(dtype, ncols, rowptr_t_ptr, rows_t_ptr, nnz, x_ptr, ld
     check(lib().pygim_spmm_softmax_backward(int(dtype), int(ncols), _vp(rowptr_t_ptr), _vp(rows_t_ptr), int(nnz), _vp(x_ptr), int(ldx), _vp(t_ptr), int(h),
                                             _vp(g_ptr), int(ldg), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(dx_ptr), int(ldd), _vp(dt_ptr), _vp(ws_ptr),
                                             int(ws_bytes), _vp(stream)))
+
+
+def spmm_edge_workspace(dtype, op, nrows, nnz, h):
+    """bytes of scratch spmm_edge needs for this type, fold (REDUCE_SUM / _MEAN / _MAX / _MIN) and shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_edge_workspace(int(dtype), int(op), int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_edge_workspace arguments")
+    return n
+
+
+def spmm_edge(dtype, op, act, eps, nrows, rowptr_ptr, col_ptr, nnz, x_ptr, ldx, e_ptr, lde, h, out_ptr, ldo, arg_ptr, ws_ptr, ws_bytes, stream=0):
+    """out[r, f] = sum / mean / max / min over the entries e of row r of act(X[col[e], f] + E[e, f]) + eps (REDUCE_*, ACT_*), in one gather with
+    E [nnz, h] read as a stream; arg_ptr: int32 [nrows, h] for the winning entry of max / min, or 0"""
+    check(lib().pygim_spmm_edge(int(dtype), int(op), int(act), float(eps), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr), int(ldx),
+                                _vp(e_ptr), int(lde), int(h), _vp(out_ptr), int(ldo), _vp(arg_ptr), _vp(ws_ptr), int(ws_bytes), _vp(stream)))
+
+
+def spmm_edge_softmax_workspace(dtype, nrows, nnz, h):
+    """bytes of scratch spmm_edge_softmax needs for this type and shape (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_edge_softmax_workspace(int(dtype), int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_edge_softmax_workspace arguments")
+    return n
+
+
+def spmm_edge_softmax(dtype, act, eps, nrows, rowptr_ptr, col_ptr, nnz, x_ptr, ldx, e_ptr, lde, t_ptr, h, out_ptr, ldo, lse_ptr, ws_ptr, ws_bytes, stream=0):
+    """spmm_softmax of the messages act(X[col[e], f] + E[e, f]) + eps; t_ptr: [h] and lse_ptr: [nrows, h] or 0, in the compute type"""
+    check(lib().pygim_spmm_edge_softmax(int(dtype), int(act), float(eps), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr), int(ldx),
+                                        _vp(e_ptr), int(lde), _vp(t_ptr), int(h), _vp(out_ptr), int(ldo), _vp(lse_ptr), _vp(ws_ptr), int(ws_bytes),
+                                        _vp(stream)))
+
+
+def spmm_edge_backward_workspace(dtype, op, nrows, nnz, h):
+    """the rows of dT_part: the runs of 512 entries (a function of the numbers alone)"""
+    n = int(lib().pygim_spmm_edge_backward_workspace(int(dtype), int(op), int(nrows), int(nnz), int(h)))
+    if n < 0:
+        raise PygimError(ERR_INVALID, "bad spmm_edge_backward_workspace arguments")
+    return n
+
+
+def spmm_edge_backward(dtype, op, act, eps, nrows, rowptr_ptr, col_ptr, nnz, x_ptr, ldx, e_ptr, lde, g_ptr, ldg, arg_ptr, t_ptr, out_ptr, ldo, lse_ptr, h,
+                       de_ptr, ldde, dt_part_ptr, stream=0):
+    """dE [nnz, h] of spmm_edge (REDUCE_SUM / _MEAN / _MAX / _MIN, with arg_ptr for max / min) or spmm_edge_softmax (REDUCE_SOFTMAX, with
+    t_ptr, out_ptr, lse_ptr; dt_part_ptr: [runs, h] in the compute type, whose column sum is the gradient of t, or 0), in entry order"""
+    check(lib().pygim_spmm_edge_backward(int(dtype), int(op), int(act), float(eps), int(nrows), _vp(rowptr_ptr), _vp(col_ptr), int(nnz), _vp(x_ptr),
+                                         int(ldx), _vp(e_ptr), int(lde), _vp(g_ptr), int(ldg), _vp(arg_ptr), _vp(t_ptr), _vp(out_ptr), int(ldo),
+                                         _vp(lse_ptr), int(h), _vp(de_ptr), int(ldde), _vp(dt_part_ptr), _vp(stream)))
 
 
 def gather_launch_shape(kind, dtype, h, heads=1, aligned=True):

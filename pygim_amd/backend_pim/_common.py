@@ -222,6 +222,15 @@ class SparseGroupBase:
 
         return matmul_softmax(self, B, t)
 
+    def mul_edge(self, B: torch.Tensor, E: torch.Tensor, reduce="sum", act=None, eps=0.0, t=1.0):
+        """aggregation of messages with a feature-wide edge feature on the raw tensor's structure with unit weights,
+        ``out[r, f] = REDUCE_e (act(B[col[e], f] + E[e, f]) + eps)`` (``pygim_amd.reduce.spmm_edge``: GINEConv, GENConv with ``edge_dim``),
+        from one gather; E [nnz, h] in the stored (row-major CSR) order of the entries.  reduce: sum, mean, max, min or softmax (with the
+        temperature t).  No group is created or used.  Differentiable in B, E and t."""
+        from ..reduce import matmul_edge
+
+        return matmul_edge(self, B, E, reduce, act, eps, t)
+
     # -- partitioning -----------------------------------------------------------
     def col_split(self, nparts=4):
         assert nparts > 0

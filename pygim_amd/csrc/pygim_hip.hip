@@ -34,6 +34,7 @@
 #include "spmm_reduce_dev.hpp"
 #include "spmm_multi_dev.hpp"
 #include "spmm_softmax_dev.hpp"
+#include "spmm_edge_dev.hpp"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
@@ -596,7 +597,7 @@ int pygim_dequantize(int dtype, const void *Q, int64_t n, const uint32_t *absmax
 
 }  // extern "C"
 
-// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward, spmm_multi_reduce, spmm_softmax and its backward ----
+// ---- functional entry points on a caller's CSR: sddmm, spmm_values, edge_softmax, gat_aggregate, spmm_reduce and its backward, spmm_multi_reduce, spmm_softmax and its backward, spmm_edge / spmm_edge_softmax and their backward ----
 // f(T()) with T the element type of `dtype` (the caller has checked it); INTS = false: FLT32 / DBL64 only
 template <bool INTS = false, typename F> static void with_elem_type(int dtype, F &&f) {
     if constexpr (INTS) {
@@ -1199,6 +1200,115 @@ int pygim_spmm_softmax_backward(int dtype, int64_t ncols, const int32_t *rowptr_
     return 0;
 }
 
+// ---- messages with a feature-wide edge feature: act(X[col] + E) + eps, folded per row; the gradient of E in entry order ----
+static bool edge_fold_op(int op) { return op == PYGIM_REDUCE_SUM || op == PYGIM_REDUCE_MEAN || op == PYGIM_REDUCE_MAX || op == PYGIM_REDUCE_MIN; }
+static bool edge_best_op(int op) { return op == PYGIM_REDUCE_MAX || op == PYGIM_REDUCE_MIN; }
+// the type an op takes: the four gather types, FLT32 / DBL64 alone for max / min
+static bool edge_type_ok(int dtype, int op) { return edge_best_op(op) ? is_float_type(dtype) : is_gather_type(dtype); }
+// op (softmax: whether the entry point has that fold), act, eps and the type, in the order the header lists them; 0 when all are fine
+static int check_edge_message(const char *name, int dtype, int op, bool softmax_ok, int act, double eps) {
+    const std::string o(name);
+    if (!(edge_fold_op(op) || (softmax_ok && op == PYGIM_REDUCE_SOFTMAX)))
+        return fail(PYGIM_ERR_INVALID, o + ": op must be PYGIM_REDUCE_SUM, _MEAN, _MAX or _MIN" + (softmax_ok ? " or _SOFTMAX" : ""));
+    if (act != PYGIM_ACT_NONE && act != PYGIM_ACT_RELU) return fail(PYGIM_ERR_INVALID, o + ": act must be PYGIM_ACT_NONE or PYGIM_ACT_RELU");
+    if (eps != eps) return fail(PYGIM_ERR_INVALID, o + ": eps is NaN");
+    if (!edge_type_ok(dtype, op))
+        return fail(PYGIM_ERR_INVALID, o + ": type must be FLT32, DBL64, FLT16 or BF16 (max / min: FLT32 or DBL64)");
+    return 0;
+}
+
+int64_t pygim_spmm_edge_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
+    static_assert(RD_SUM == PYGIM_REDUCE_SUM && RD_SOFTMAX == PYGIM_REDUCE_SOFTMAX && RD_MEAN == PYGIM_REDUCE_MEAN && RD_MAX == PYGIM_REDUCE_MAX &&
+                      RD_MIN == PYGIM_REDUCE_MIN && EM_ACT_RELU == PYGIM_ACT_RELU,
+                  "the codes of include/pygim_hip.h");
+    if (!edge_fold_op(op) || !edge_type_ok(dtype, op)) return -1;
+    if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
+    return (int64_t)spmm_edge_workspace_bytes(op, (uint64_t)nnz, (uint64_t)h, gather_compute_size(dtype));
+}
+
+int pygim_spmm_edge(int dtype, int op, int act, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X,
+                    int64_t ldx, const void *E, int64_t lde, int64_t h, void *out, int64_t ldo, int32_t *arg, void *workspace, int64_t workspace_bytes,
+                    void *stream) {
+    if (int rc = check_edge_message("spmm_edge", dtype, op, false, act, eps)) return rc;
+    if (!edge_best_op(op) && arg) return fail(PYGIM_ERR_INVALID, "spmm_edge: sum and mean have no arg output");
+    if (arg && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_edge: arg must be 4-byte aligned");
+    if (h >= 1 && lde < h) return fail(PYGIM_ERR_INVALID, "bad spmm_edge sizes / strides");
+    if (int rc = check_csr_call("spmm_edge", "rowptr / colind / X / E / out", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {arg, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {E, nnz > 0}},
+                                pygim_spmm_edge_workspace(dtype, op, nrows, nnz, h), workspace, workspace_bytes))
+        return rc;
+    if (int rc = need_init()) return rc;   // after the argument checks: they need no device
+    with_gather_types(dtype, [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        const EdgeMsg<T> msg = {(T)eps, act == PYGIM_ACT_RELU};
+        launch_spmm_edge<T, S>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)X, (uint64_t)ldx, (const S *)E,
+                               (uint64_t)lde, msg, (uint32_t)h, (S *)out, (uint64_t)ldo, arg, workspace, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t pygim_spmm_edge_softmax_workspace(int dtype, int64_t nrows, int64_t nnz, int64_t h) { return pygim_spmm_softmax_workspace(dtype, nrows, nnz, h); }
+
+int pygim_spmm_edge_softmax(int dtype, int act, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X, int64_t ldx,
+                            const void *E, int64_t lde, const void *t, int64_t h, void *out, int64_t ldo, void *lse, void *workspace, int64_t workspace_bytes,
+                            void *stream) {
+    if (int rc = check_edge_message("spmm_edge_softmax", dtype, PYGIM_REDUCE_SOFTMAX, true, act, eps)) return rc;
+    if (h >= 1 && lde < h) return fail(PYGIM_ERR_INVALID, "bad spmm_edge_softmax sizes / strides");
+    if (int rc = check_csr_call("spmm_edge_softmax", "rowptr / colind / X / E / t / out / lse", nrows, nnz, 0x7FFFFFFFll, h, (int64_t)RG_MAX_H, ldx, ldo,
+                                {{rowptr, true}, {out, nrows > 0}, {lse, nrows > 0, true}, {colind, nnz > 0}, {X, nnz > 0}, {E, nnz > 0}, {t, nnz > 0}},
+                                pygim_spmm_edge_softmax_workspace(dtype, nrows, nnz, h), workspace, workspace_bytes))
+        return rc;
+    if (lse && (uintptr_t)lse % gather_compute_size(dtype) != 0) return fail(PYGIM_ERR_INVALID, "spmm_edge_softmax: lse must be aligned to its element");
+    if (int rc = need_init()) return rc;   // after the argument checks: they need no device
+    with_gather_types(dtype, [&](auto tt, auto s) {
+        using T = decltype(tt);
+        using S = decltype(s);
+        const EdgeMsg<T> msg = {(T)eps, act == PYGIM_ACT_RELU};
+        launch_spmm_edge_softmax<T, S>((const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)X, (uint64_t)ldx,
+                                       (const S *)E, (uint64_t)lde, msg, (const T *)t, (uint32_t)h, (S *)out, (uint64_t)ldo, (T *)lse, workspace,
+                                       (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the rows of dT_part: one per run of RG_EPW entries
+int64_t pygim_spmm_edge_backward_workspace(int dtype, int op, int64_t nrows, int64_t nnz, int64_t h) {
+    if (!(edge_fold_op(op) || op == PYGIM_REDUCE_SOFTMAX) || !edge_type_ok(dtype, op)) return -1;
+    if (nrows < 0 || nnz < 0 || nnz > 0x7FFFFFFFll || h < 1 || h > (int64_t)RG_MAX_H) return -1;
+    return (int64_t)row_gather_runs((uint64_t)nnz);
+}
+
+int pygim_spmm_edge_backward(int dtype, int op, int act, double eps, int64_t nrows, const int32_t *rowptr, const int32_t *colind, int64_t nnz, const void *X,
+                             int64_t ldx, const void *E, int64_t lde, const void *G, int64_t ldg, const int32_t *arg, const void *t, const void *out, int64_t ldo,
+                             const void *lse, int64_t h, void *dE, int64_t ldde, void *dT_part, void *stream) {
+    if (int rc = check_edge_message("spmm_edge_backward", dtype, op, true, act, eps)) return rc;
+    const bool softmax = op == PYGIM_REDUCE_SOFTMAX, best = edge_best_op(op);
+    if (h >= 1 && (lde < h || ldg < h || (softmax && ldo < h))) return fail(PYGIM_ERR_INVALID, "bad spmm_edge_backward sizes / strides");
+    if (dT_part && !softmax) return fail(PYGIM_ERR_INVALID, "spmm_edge_backward: dT_part belongs to PYGIM_REDUCE_SOFTMAX");
+    if (int rc = check_csr_call("spmm_edge_backward", "rowptr / colind / X / E / G / arg / t / out / lse / dE / dT_part", nrows, nnz, 0x7FFFFFFFll, h,
+                                (int64_t)RG_MAX_H, ldx, ldde,
+                                {{rowptr, true}, {colind, nnz > 0}, {X, nnz > 0}, {E, nnz > 0}, {G, nnz > 0}, {dE, nnz > 0}, {arg, nnz > 0 && best},
+                                 {t, nnz > 0 && softmax}, {out, nnz > 0 && softmax}, {lse, nnz > 0 && softmax}, {dT_part, nnz > 0, true}}))
+        return rc;
+    if (nnz > 0 && best && (uintptr_t)arg % 4 != 0) return fail(PYGIM_ERR_INVALID, "spmm_edge_backward: arg must be 4-byte aligned");
+    if (nnz > 0 && softmax && ((uintptr_t)lse % gather_compute_size(dtype) != 0 || (dT_part && (uintptr_t)dT_part % gather_compute_size(dtype) != 0)))
+        return fail(PYGIM_ERR_INVALID, "spmm_edge_backward: lse and dT_part must be aligned to their element");
+    if (int rc = need_init()) return rc;   // after the argument checks: they need no device
+    with_gather_types(dtype, [&](auto tt, auto s) {
+        using T = decltype(tt);
+        using S = decltype(s);
+        const EdgeMsg<T> msg = {(T)eps, act == PYGIM_ACT_RELU};
+        launch_spmm_edge_backward<T, S>(op, (const uint32_t *)rowptr, (const uint32_t *)colind, (uint32_t)nrows, (uint32_t)nnz, (const S *)X, (uint64_t)ldx,
+                                        (const S *)E, (uint64_t)lde, msg, (uint32_t)h, (const S *)G, (uint64_t)ldg, arg, (const T *)t, (const S *)out,
+                                        (uint64_t)ldo, (const T *)lse, (S *)dE, (uint64_t)ldde, (T *)dT_part, (hipStream_t)stream);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the launch shape of a gather entry point, from the functions its launcher calls; no device, no launch (like the *_workspace functions)
 int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int aligned, int64_t out[8]) {
     static_assert(LS_PART_PIECE == PYGIM_SHAPE_PART_PIECE && LS_PART_CHUNK == PYGIM_SHAPE_PART_CHUNK && LS_PART_HEADS == PYGIM_SHAPE_PART_HEADS &&
@@ -1208,7 +1318,7 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     const bool head_wise = kind == PYGIM_SHAPE_SPARSE_ATTENTION || kind == PYGIM_SHAPE_GATV2_AGGREGATE || kind == PYGIM_SHAPE_GATV2_BACKWARD;
     const bool walker = kind == PYGIM_SHAPE_SPMM_VALUES || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_GAT_AGGREGATE ||
                         kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD || kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE || kind == PYGIM_SHAPE_SPMM_SOFTMAX ||
-                        kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD;
+                        kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD || kind == PYGIM_SHAPE_SPMM_EDGE || kind == PYGIM_SHAPE_SPMM_EDGE_BACKWARD;
     bool type_ok;
     if (kind == PYGIM_SHAPE_SPMM_REDUCE) type_ok = dtype_size(dtype) != 0 || is_half_type(dtype);   // integers: max / min; 16-bit: the mean
     else if (kind == PYGIM_SHAPE_EDGE_SOFTMAX || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) type_ok = is_float_type(dtype);
@@ -1217,6 +1327,7 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     if (kind == PYGIM_SHAPE_SDDMM || kind == PYGIM_SHAPE_SPMM_REDUCE || kind == PYGIM_SHAPE_SPMM_REDUCE_BACKWARD) heads = 1;   // they have none
     if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE && heads != 1) return PYGIM_ERR_INVALID;   // it has none either, and says so: heads must be 1
     if ((kind == PYGIM_SHAPE_SPMM_SOFTMAX || kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD) && heads != 1) return PYGIM_ERR_INVALID;   // nor have these
+    if ((kind == PYGIM_SHAPE_SPMM_EDGE || kind == PYGIM_SHAPE_SPMM_EDGE_BACKWARD) && heads != 1) return PYGIM_ERR_INVALID;         // nor these
     if (kind == PYGIM_SHAPE_EDGE_SOFTMAX) h = heads;                                                                           // it has no h
     if (h < 1 || heads < 1 || heads > 0x7FFFFFFFll || h % heads != 0 || h > (walker ? (int64_t)RG_MAX_H : 0xFFFFFFFFll)) return PYGIM_ERR_INVALID;
     if (head_wise && h / heads > (int64_t)SA_MAX_HEAD) return PYGIM_ERR_INVALID;
@@ -1229,6 +1340,8 @@ int pygim_gather_launch_shape(int kind, int dtype, int64_t h, int64_t heads, int
     else if (kind == PYGIM_SHAPE_SPMM_MULTI_REDUCE) g = multi_gather_shape((uint32_t)h, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_SPMM_SOFTMAX) g = softmax_gather_shape((uint32_t)h, V, aligned != 0);
     else if (kind == PYGIM_SHAPE_SPMM_SOFTMAX_BACKWARD) g = softmax_grad_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_EDGE) g = edge_gather_shape((uint32_t)h, V, aligned != 0);
+    else if (kind == PYGIM_SHAPE_SPMM_EDGE_BACKWARD) g = edge_grad_shape((uint32_t)h, V, aligned != 0);
     else g = row_gather_shape((uint32_t)h, (uint32_t)(h / heads), V, aligned != 0);
     const int64_t v[8] = {g.vec, g.npl, g.LH, g.L, g.per, g.chunks, g.launches, g.flags};
     for (int i = 0; i < 8; i++) out[i] = v[i];

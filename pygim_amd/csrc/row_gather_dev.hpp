@@ -28,7 +28,8 @@
 //     launch_multi_gather_v, launch_softmax_gather_v and launch_softmax_grad_v.
 //   * The walk inside the gather kernel -- batch loop, row search, ballot of row ends, cut into stretches, slot rule -- is still copied
 //     text in k_gat_gather, k_multi_gather, k_sa_gather (sparse_attention_dev.hpp), k_gatv2_gather and k_gatv2_grad (gatv2_dev.hpp),
-//     k_softmax_gather and k_softmax_grad (spmm_softmax_dev.hpp): a change to the walk here has to be made in those seven as well.  One device function for it, taking the kernel's per-batch
+//     k_softmax_gather and k_softmax_grad (spmm_softmax_dev.hpp), k_edge_gather, k_edge_softmax_gather and k_edge_message_grad
+//     (spmm_edge_dev.hpp): a change to the walk here has to be made in those ten as well.  One device function for it, taking the kernel's per-batch
 //     load, its fold of a stretch and its row close as three lambdas, was written and measured (profiles/walker_refactor_resources.txt):
 //     every call inlines and no form uses scratch, but a fold body that is optimised as a function of its own before it is inlined does
 //     not come out as the same body written in the kernel, and in every form tried some instantiations lose a wave per SIMD (27 of

@@ -32,9 +32,13 @@ PNAConv / PNA are PyG's PNAConv with one tower, one linear pre-layer and no edge
 mean, min, max and std (or any of sum / mean / min / max / var / std) of the neighbours' messages come from one gather per layer, no
 ``[E, F]`` message tensor is formed; identity / amplification / attenuation scalers; float32 / float64, bfloat16 like ``SAGEConv(aggr="mean")``.
 
-GENConv / GEN are PyG's GENConv (DeeperGCN, Li et al.) without edge features on ``pygim_amd.reduce.spmm_softmax``: the softmax aggregation
+GENConv / GEN are PyG's GENConv (DeeperGCN, Li et al.) on ``pygim_amd.reduce.spmm_softmax``: the softmax aggregation
 of the neighbours' messages per feature, with a fixed or learnable temperature, is one gather per layer forward and one backward, no
 ``[E, F]`` tensor; ``aggr="mean"`` / ``"max"`` / ``"sum"`` go through the functions that exist; the same dtypes as PNAConv.
+``GENEConv(in, out, edge_dim, ...)`` is GENConv with PyG's edge features, ``forward(x, adj_t, edge_attr)``: the message ``relu(x_j + e_ij) + eps`` is formed
+inside the gather (``pygim_amd.reduce.spmm_edge``), the edge features read as a stream beside it.
+
+GINEConv / GINE are PyG's GINEConv (Hu et al.): ``nn((1 + eps) * x_i + sum_j relu(x_j + e_ij))`` on ``spmm_edge`` with the sum fold.
 """
 import torch
 import torch.nn.functional as F
@@ -88,6 +92,49 @@ class GINConv(torch.nn.Module):
 
     def forward(self, x, adj_t):
         return self.nn(message_and_aggregate(adj_t, x) + (1 + self.eps) * x)
+
+
+class GINEConv(torch.nn.Module):
+    """PyG's GINEConv: ``out_i = nn((1 + eps) * x_i + sum_j relu(x_j + e_ij))`` over the stored entries (i, j) of the adjacency as given.
+    ``forward(x, adj_t, edge_attr)`` takes ``edge_attr`` [nnz, edge_dim] (or [nnz, in_channels] without ``edge_dim``) in the stored order of
+    the adjacency (``EdgeGraph.of(adj_t).row`` / ``.col``: row-major CSR order); with ``edge_dim`` a ``Linear(edge_dim, in_channels)`` maps it
+    to the node width first (``in_channels``: that of ``nn``'s first Linear, as in PyG).  The sum runs in ONE ``spmm_edge`` gather
+    (``fused=True``, the default) that reads the edge features as a stream -- no ``[nnz, F]`` message tensor -- or through the composition
+    ``relu(x[col] + e)`` (``fused=False``).  ``train_eps``: eps is a parameter.  float32 / float64, trainable; bfloat16 after
+    ``.to(torch.bfloat16)`` or under ``torch.autocast``; one GPU."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False, edge_dim=None, fused=True, **_):
+        super().__init__()
+        self.nn, self.fused = nn, bool(fused)
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.tensor(float(eps)))
+        else:
+            self.register_buffer("eps", torch.tensor(float(eps)))
+        self.lin = None
+        if edge_dim is not None:
+            first = nn[0] if isinstance(nn, Sequential) else nn
+            width = getattr(first, "in_features", getattr(first, "in_channels", None))
+            if width is None:
+                raise ValueError("GINEConv: could not infer the input width from nn (its first module needs in_features or in_channels)")
+            if int(edge_dim) < 1:
+                raise ValueError(f"GINEConv: edge_dim must be at least 1, got {edge_dim}")
+            self.lin = Linear(int(edge_dim), int(width))
+
+    def forward(self, x, adj_t, edge_attr):
+        if getattr(adj_t, "row_sharded", False):
+            raise NotImplementedError("GINEConv is not available on a RowShardAdj (one GPU only)")
+        from .reduce import matmul_edge
+
+        if self.lin is not None and (edge_attr.dim() != 2 or edge_attr.size(1) != self.lin.in_features):
+            raise ValueError(f"GINEConv: edge_attr must be [nnz, {self.lin.in_features}], got {tuple(edge_attr.shape)}")
+        e = edge_attr if self.lin is None else self.lin(edge_attr)
+        if e.dim() != 2 or e.size(1) != x.size(1):
+            raise ValueError(f"GINEConv: node features of width {x.size(1)} need edge features of that width (set edge_dim), got {tuple(e.shape)}")
+        if e.dtype != x.dtype:   # under autocast lin gives 16 bits beside float32 x: the wider of the two
+            wide = torch.promote_types(e.dtype, x.dtype)
+            x, e = x.to(wide), e.to(wide)
+        agg = matmul_edge(adj_t, x, e, "sum", "relu", 0.0, fused=self.fused)
+        return self.nn(agg + (1 + self.eps).to(agg.dtype) * x)
 
 
 class GATConv(torch.nn.Module):
@@ -313,7 +360,7 @@ class PNAConv(torch.nn.Module):
 
 
 class GENConv(torch.nn.Module):
-    """PyG's GENConv (Li et al., DeeperGCN) without edge features, on the adjacency as given:
+    """PyG's GENConv (Li et al., DeeperGCN) on the adjacency as given:
     message of stored entry (i, j) = relu(x_src[j]) + eps;  agg_i = the aggregation of the messages over the entries of row i;
     out = mlp(agg + x_dst),  x_src = lin_src(x) and x_dst = lin_dst(x) when ``in_channels != out_channels`` (else x itself),
     mlp = Linear -> norm -> ReLU -> Linear (``num_layers`` linear maps, hidden width ``expansion * out_channels``).
@@ -323,15 +370,21 @@ class GENConv(torch.nn.Module):
     ``learn_t``), ONE ``spmm_softmax`` gather (``fused=True``, the default: the composition holds ``[nnz, out_channels]`` tensors) or its
     composition from ``edge_softmax`` and ``spmm_values`` (``fused=False``).  ``"mean"``, ``"max"``, ``"sum"``: ``spmm_reduce`` /
     ``spmm_values`` with unit weights.  Rows without entries aggregate to 0.
+    This class takes no edge features (``edge_dim`` and ``edge_attr`` raise NotImplementedError, as they always did): :class:`GENEConv` is
+    the layer with them.
     float32 / float64, trainable; bfloat16 after ``.to(torch.bfloat16)`` or under ``torch.autocast`` (softmax, mean, sum); one GPU."""
+
+    EDGE_FEATURES = False   # GENEConv: True
 
     def __init__(self, in_channels, out_channels, aggr="softmax", t=1.0, learn_t=False, eps=1e-7, num_layers=2, expansion=2, norm="batch", bias=True,
                  fused=True, edge_dim=None, learn_p=False, msg_norm=False, **_):
         super().__init__()
         if aggr in ("powermean", "power"):
             raise NotImplementedError("GENConv: aggr='powermean' is not implemented (softmax, mean, max and sum are)")
-        if edge_dim is not None:
-            raise NotImplementedError("GENConv: edge features (edge_dim) are not implemented")
+        if edge_dim is not None and not self.EDGE_FEATURES:
+            raise NotImplementedError("GENConv: edge features (edge_dim) are not implemented in this class; GENEConv(in, out, edge_dim) is the layer with them")
+        if edge_dim is not None and int(edge_dim) < 1:
+            raise ValueError(f"GENEConv: edge_dim must be at least 1, got {edge_dim}")
         if learn_p or msg_norm:
             raise NotImplementedError("GENConv: learn_p and msg_norm are not implemented")
         if aggr not in ("softmax", "mean", "max", "sum", "add"):
@@ -357,17 +410,31 @@ class GENConv(torch.nn.Module):
                     layers.append(BatchNorm1d(widths[i + 1]) if norm == "batch" else torch.nn.LayerNorm(widths[i + 1]))
                 layers.append(ReLU())
         self.mlp = Sequential(*layers)
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+        self.lin_edge = None
+        if self.edge_dim is not None and self.edge_dim != self.out_channels:   # created last, so that the other parameters draw what they drew without edge_dim
+            self.lin_edge = Linear(self.edge_dim, self.out_channels, bias=bias)
 
     def forward(self, x, adj_t, edge_attr=None):
-        if edge_attr is not None:
-            raise NotImplementedError("GENConv: edge features are not implemented")
+        if edge_attr is not None and self.edge_dim is None:
+            raise NotImplementedError("GENConv: edge features are not implemented in this class; GENEConv(in, out, edge_dim) is the layer with them")
         if getattr(adj_t, "row_sharded", False):
             raise NotImplementedError("GENConv is not available on a RowShardAdj (one GPU only)")
         from .attention import EdgeGraph, _compute_dtype, spmm_values
-        from .reduce import spmm_reduce, spmm_softmax
+        from .reduce import spmm_edge, spmm_reduce, spmm_softmax
 
         g = EdgeGraph.of(adj_t)
         src = x if self.lin_src is None else self.lin_src(x)
+        if edge_attr is not None:
+            if edge_attr.dim() != 2 or edge_attr.size(1) != self.edge_dim:
+                raise ValueError(f"GENEConv: edge_attr must be [nnz, {self.edge_dim}], got {tuple(edge_attr.shape)}")
+            e = edge_attr if self.lin_edge is None else self.lin_edge(edge_attr)
+            if e.dtype != src.dtype:   # under autocast the two Linears give 16 bits beside float32 operands: the wider of the two
+                wide = torch.promote_types(e.dtype, src.dtype)
+                src, e = src.to(wide), e.to(wide)
+            agg = spmm_edge(g, src, e, self.aggr, "relu", self.eps, self.t, fused=self.fused)
+            dst = x if self.lin_dst is None else self.lin_dst(x)
+            return self.mlp(agg + dst.to(agg.dtype))
         msg = F.relu(src) + self.eps
         if self.aggr == "softmax":
             agg = spmm_softmax(g, msg, self.t, fused=self.fused)
@@ -377,6 +444,23 @@ class GENConv(torch.nn.Module):
             agg = spmm_reduce(g, msg, self.aggr)
         dst = x if self.lin_dst is None else self.lin_dst(x)
         return self.mlp(agg + dst.to(agg.dtype))
+
+
+class GENEConv(GENConv):
+    """GENConv with PyG's edge features (PyG's ``GENConv(edge_dim=)``; a class of its own, as GINEConv is beside GINConv).
+    ``forward(x, adj_t, edge_attr)`` takes ``edge_attr`` [nnz, edge_dim] in the stored order of the adjacency (``EdgeGraph.of(adj_t).row`` /
+    ``.col``: row-major CSR order); the message is ``relu(x_src[j] + e_ij) + eps`` with ``e = lin_edge(edge_attr)`` (a Linear when
+    ``edge_dim != out_channels``, as in PyG, else ``edge_attr`` itself), formed inside ONE ``spmm_edge`` gather for every ``aggr`` -- softmax
+    with ``learn_t``, mean, max, sum -- that reads the edge features as a stream (``fused=False``: through the ``[nnz, out_channels]``
+    message tensor).  ``edge_attr=None`` gives GENConv's own forward.  The other arguments, the dtypes and the parameters drawn before
+    ``lin_edge`` are GENConv's."""
+
+    EDGE_FEATURES = True
+
+    def __init__(self, in_channels, out_channels, edge_dim, **kw):
+        if edge_dim is None:
+            raise ValueError("GENEConv: edge_dim is needed (GENConv is the layer without edge features)")
+        super().__init__(in_channels, out_channels, edge_dim=edge_dim, **kw)
 
 
 def _att_dropout(name, p):
@@ -417,7 +501,8 @@ class _Stack(torch.nn.Module):
                 a, b = folded_epilogue(conv.bias, bn)
                 x, _ = adj_t.mul_quantized(conv.lin(x), post=(a, b, True))
                 continue
-            x = F.dropout(F.relu(bn(conv(x, adj_t))), p=self.dropout, training=self.training)
+            out = conv(x, adj_t) if edge_attr is None else conv(x, adj_t, edge_attr)
+            x = F.dropout(F.relu(bn(out)), p=self.dropout, training=self.training)
         return self.ln2(x)
 
 
@@ -435,6 +520,15 @@ class GIN(_Stack):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5):
         mlp = lambda h: Sequential(Linear(h, h), BatchNorm1d(h), ReLU(), Linear(h, h))
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout, lambda h: GINConv(mlp(h)))
+
+
+class GINE(_Stack):
+    """a stack of GINEConv layers; ``forward(x, adj_t, edge_attr)`` hands the same ``edge_attr`` [nnz, edge_dim] to every layer"""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, edge_dim, num_layers=2, dropout=0.5, train_eps=False, fused=True):
+        mlp = lambda h: Sequential(Linear(h, h), BatchNorm1d(h), ReLU(), Linear(h, h))
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
+                         lambda h: GINEConv(mlp(h), train_eps=train_eps, edge_dim=edge_dim, fused=fused))
 
 
 class GAT(_Stack):
@@ -462,9 +556,10 @@ class PNA(_Stack):
 
 class GEN(_Stack):
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, aggr="softmax", t=1.0, learn_t=False, norm="batch",
-                 fused=True):
+                 fused=True, edge_dim=None):
         super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout,
-                         lambda h: GENConv(h, h, aggr=aggr, t=t, learn_t=learn_t, norm=norm, fused=fused))
+                         lambda h: (GENConv(h, h, aggr=aggr, t=t, learn_t=learn_t, norm=norm, fused=fused) if edge_dim is None else
+                                    GENEConv(h, h, edge_dim, aggr=aggr, t=t, learn_t=learn_t, norm=norm, fused=fused)))
 
 
 class GraphTransformer(_Stack):

@@ -25,8 +25,15 @@ run).  Sums stay with ``mul`` / ``spmm_values``.
   takes the probabilities again from the saved log-sum-exp).  float32 / float64 / bfloat16 / float16; differentiable in X and t;
   ``fused=False`` composes it from ``edge_softmax`` and ``spmm_values`` with ``heads = h`` through ``[nnz, h]`` tensors.
 
+* ``spmm_edge``: messages with a feature-wide edge feature, ``msg[e, f] = act(X[col[e], f] + E[e, f]) + eps`` (GINEConv; GENConv with
+  ``edge_dim``), folded per row with sum, mean, max, min or the softmax above (pygim_spmm_edge / pygim_spmm_edge_softmax: the gather of the
+  same fold with ``E [nnz, h]`` read as a stream beside it; pygim_spmm_edge_backward: ``dE`` in one entry-order kernel, and ``dX`` as the
+  sum of the ``dE`` rows per column through ``pygim_spmm_values`` on the transposed structure).  float32 / float64 / bfloat16 / float16
+  (max / min: float32 / float64); differentiable in X, E and t; ``fused=False`` composes it through ``X[col] + E``.
+
 Not covered: the gradient of max / min with respect to ``value`` (it needs a masked SDDMM), double backward, integer mean,
-multi-head values, edge weights or integer types in ``spmm_multi_reduce`` and ``spmm_softmax``, ``RowShardAdj`` / multi-GPU.
+multi-head values, edge weights or integer types in ``spmm_multi_reduce``, ``spmm_softmax`` and ``spmm_edge``, forming ``E = edge_attr @ W``
+inside the kernel, ``powermean``, ``RowShardAdj`` / multi-GPU.
 """
 from __future__ import annotations
 
@@ -447,3 +454,179 @@ def matmul_softmax(adj, B: torch.Tensor, t=1.0, fused: bool = True):
     if getattr(adj, "row_sharded", False):
         raise NotImplementedError("matmul_softmax is not available on a RowShardAdj (one GPU only)")
     return spmm_softmax(EdgeGraph.of(adj), B, t, fused=fused)
+
+
+# ---- messages with a feature-wide edge feature: act(X[col] + E) + eps, folded per row ----
+EDGE_REDUCE_CODE = {"sum": 4, "mean": 1, "max": 2, "min": 3, "softmax": 5}   # PYGIM_REDUCE_* (softmax: pygim_spmm_edge_backward's code)
+ACT_CODE = {None: 0, "relu": 1}                                               # PYGIM_ACT_*
+
+
+def _run_spmm_edge(g: EdgeGraph, X, E, reduce: str, act: int, eps: float, tv, want_arg: bool, want_lse: bool):
+    """X [ncols, h], E [nnz, h] contiguous on g.device, tv [h] (compute dtype) for the softmax -> (out [nrows, h], arg int32 or None, lse or None)"""
+    L, _ = _backend()
+    dt = _gather_code(X.dtype)
+    h = X.size(1)
+    out = torch.empty((g.nrows, h), dtype=X.dtype, device=g.device)
+    arg = torch.empty((g.nrows, h), dtype=torch.int32, device=g.device) if want_arg else None
+    lse = torch.empty((g.nrows, h), dtype=_compute_dtype(X.dtype), device=g.device) if want_lse else None
+    if g.nrows == 0:
+        return out, arg, lse
+    if reduce == "softmax":
+        ws = _workspace(L.spmm_edge_softmax_workspace(dt, g.nrows, g.nnz, h), g.device)
+        L.spmm_edge_softmax(dt, act, eps, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), E.data_ptr(), E.stride(0),
+                            tv.data_ptr(), h, out.data_ptr(), h, 0 if lse is None else lse.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device))
+    else:
+        op = EDGE_REDUCE_CODE[reduce]
+        ws = _workspace(L.spmm_edge_workspace(dt, op, g.nrows, g.nnz, h), g.device)
+        L.spmm_edge(dt, op, act, eps, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), E.data_ptr(), E.stride(0), h,
+                    out.data_ptr(), h, 0 if arg is None else arg.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device))
+    return out, arg, lse
+
+
+def _sum_entries_per_column(g: EdgeGraph, dE: torch.Tensor) -> torch.Tensor:
+    """dX[c] = the sum of the rows dE[e] over the entries e of column c, in the order of A^T: pygim_spmm_values on the transposed row
+    pointer with perm as column ids, unit weights and X := dE"""
+    L, _ = _backend()
+    gt, ones = _unit_values_t(g, _compute_dtype(dE.dtype))
+    h = dE.size(1)
+    dX = torch.empty((g.ncols, h), dtype=dE.dtype, device=g.device)
+    if g.ncols == 0:
+        return dX
+    dt = _gather_code(dE.dtype)
+    ws = _workspace(L.spmm_values_workspace(dt, g.ncols, g.nnz, h, 1), g.device)
+    L.spmm_values(dt, g.ncols, gt.rowptr.data_ptr(), g.entry_ids_t().data_ptr(), g.nnz, ones.data_ptr(), 1, dE.data_ptr(), h, h, dX.data_ptr(), h,
+                  ws.data_ptr(), ws.numel(), _stream(g.device))
+    return dX
+
+
+class SpmmEdge(torch.autograd.Function):
+    """forward: one pygim_spmm_edge / pygim_spmm_edge_softmax.  backward: one pygim_spmm_edge_backward writes dE in entry order -- the only
+    [nnz, h] tensor it allocates -- and, the message being additive in x and e, dX is the sum of the dE rows per column (pygim_spmm_values
+    on the transposed structure); dt is the column sum of the runs' partial results.  Saved: X, E and arg, or out and lse."""
+
+    @staticmethod
+    def forward(ctx, g, X, E, tv, reduce, act, eps, want_arg):
+        grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or (tv is not None and ctx.needs_input_grad[3])
+        best = reduce in ("max", "min")
+        out, arg, lse = _run_spmm_edge(g, X, E, reduce, act, eps, tv, best and (want_arg or grad), reduce == "softmax" and grad)
+        ctx.g, ctx.reduce, ctx.act, ctx.eps = g, reduce, act, eps
+        if grad:
+            ctx.save_for_backward(X, E, tv, arg, out if reduce == "softmax" else None, lse)
+        arg_o = torch.empty(0, dtype=torch.int32, device=g.device) if arg is None else arg
+        ctx.mark_non_differentiable(arg_o)
+        return out, arg_o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _):
+        g, reduce = ctx.g, ctx.reduce
+        X, E, tv, arg, out, lse = ctx.saved_tensors
+        L, _c = _backend()
+        dt = _gather_code(X.dtype)
+        h = X.size(1)
+        G = G.to(X.dtype).contiguous()
+        op = EDGE_REDUCE_CODE[reduce]
+        dE = torch.empty((g.nnz, h), dtype=X.dtype, device=g.device)
+        want_dt = reduce == "softmax" and ctx.needs_input_grad[3]
+        part = None
+        if g.nnz > 0:
+            if want_dt:
+                part = torch.empty((L.spmm_edge_backward_workspace(dt, op, g.nrows, g.nnz, h), h), dtype=tv.dtype, device=g.device)
+            ptr = lambda a: 0 if a is None else a.data_ptr()
+            L.spmm_edge_backward(dt, op, ctx.act, ctx.eps, g.nrows, g.rowptr.data_ptr(), g.col.data_ptr(), g.nnz, X.data_ptr(), X.stride(0), E.data_ptr(),
+                                 E.stride(0), G.data_ptr(), h, ptr(arg), ptr(tv), ptr(out), h, ptr(lse), h, dE.data_ptr(), h, ptr(part), _stream(g.device))
+        dX = _sum_entries_per_column(g, dE) if ctx.needs_input_grad[1] else None
+        dT = None
+        if want_dt:
+            dT = part.sum(0) if part is not None else torch.zeros(h, dtype=tv.dtype, device=g.device)
+        return None, dX, (dE if ctx.needs_input_grad[2] else None), dT, None, None, None, None
+
+
+def _edge_composed(g: EdgeGraph, X, E, tv, reduce: str, act, eps: float, want_arg: bool):
+    """the same aggregation through the [nnz, h] message tensor: X[col] + E, then spmm_values with ones on an identity of the entries'
+    columns, spmm_reduce, or edge_softmax + spmm_values with heads = h.  16-bit operands are taken up to float32 and the result rounded once."""
+    from .attention import edge_softmax, spmm_values
+
+    ct = _compute_dtype(X.dtype)
+    msg = X.to(ct).index_select(0, g.col.long()) + E.to(ct)
+    if act == "relu":
+        msg = torch.relu(msg)
+    if eps != 0.0:
+        msg = msg + eps
+    # the messages as the "feature matrix" of a graph whose entry e gathers row e: the structure of A with col = arange(nnz)
+    ge = EdgeGraph._bare(g.rowptr, torch.arange(g.nnz, dtype=torch.int32, device=g.device), g.row, g.nrows, g.nnz)
+    arg = None
+    if reduce == "sum":
+        out = spmm_values(ge, torch.ones(g.nnz, dtype=ct, device=g.device), msg)
+    elif reduce == "softmax":
+        out = spmm_values(ge, edge_softmax(ge, msg * tv), msg, heads=msg.size(1))
+    elif want_arg:
+        out, arg = spmm_reduce(ge, msg, reduce, return_arg=True)
+    else:
+        out = spmm_reduce(ge, msg, reduce)
+    return out.to(X.dtype), arg
+
+
+def spmm_edge(graph, X: torch.Tensor, E: torch.Tensor, reduce: str = "sum", act=None, eps: float = 0.0, t=1.0, fused: bool = True,
+              return_arg: bool = False):
+    """``out[r, f] = REDUCE over the stored entries e of row r of act(X[col[e], f] + E[e, f]) + eps``: aggregation of messages that carry a
+    feature-wide edge feature (PyG's GINEConv and GENConv with ``edge_dim``), without the ``[nnz, h]`` message tensor
+
+    graph: an :class:`EdgeGraph` or anything ``EdgeGraph.of`` takes; X [columns, h] and E [nnz, h] of one dtype -- float32, float64,
+    bfloat16 or float16 (16-bit: float32 arithmetic, the result rounded once; max / min take float32 / float64 only) -- with the rows of
+    E in the stored order of the graph (``EdgeGraph.row`` / ``.col``); reduce: ``"sum"``, ``"mean"``, ``"max"``, ``"min"`` or ``"softmax"``
+    (``softmax_e(t[f] * msg[e, f])`` per row and feature, ``t`` as in :func:`spmm_softmax`); act: ``None`` or ``"relu"``; eps: a float added
+    after the activation.  Unit weights; empty rows give 0.  ``return_arg`` (max / min): also the int32 [rows, h] index of the entry that won,
+    -1 for empty rows; ties go to the lowest index.  Differentiable in X, E and (softmax) t: the backward writes ``dE`` in one kernel -- the
+    only ``[nnz, h]`` tensor it allocates -- and sums its rows per column for ``dX``; no double backward.  ``fused=False`` composes the same
+    result from ``X[col] + E`` and the functions that exist.  Runs on the device; CPU tensors are staged there and the results come back
+    to X's device."""
+    if reduce not in EDGE_REDUCE_CODE:
+        raise ValueError(f"spmm_edge: reduce must be 'sum', 'mean', 'max', 'min' or 'softmax', got {reduce!r}")
+    if act not in ACT_CODE:
+        raise ValueError(f"spmm_edge: act must be None or 'relu', got {act!r}")
+    if X.dtype not in FLOAT_TYPES and X.dtype not in HALF_TYPES:
+        raise TypeError(f"spmm_edge: X must be float32, float64, bfloat16 or float16, got {X.dtype}")
+    if reduce in ("max", "min") and X.dtype in HALF_TYPES:
+        raise TypeError(f"spmm_edge: unsupported element type {X.dtype} for max / min (16-bit features: sum, mean and softmax)")
+    if not torch.is_tensor(E) or E.dtype != X.dtype:
+        raise TypeError(f"spmm_edge: X and E must have one dtype, got {X.dtype} and {E.dtype if torch.is_tensor(E) else type(E).__name__}")
+    g = EdgeGraph.of(graph)
+    if X.dim() != 2 or X.size(0) != g.ncols or X.size(1) < 1:
+        raise ValueError(f"spmm_edge: X must be [{g.ncols}, h], got {tuple(X.shape)}")
+    h = X.size(1)
+    if E.dim() != 2 or E.size(0) != g.nnz or E.size(1) != h:
+        raise ValueError(f"spmm_edge: E must be [{g.nnz}, {h}] (one row per stored entry, in the order of the graph's row / col), got {tuple(E.shape)}")
+    eps = float(eps)
+    if eps != eps:
+        raise ValueError("spmm_edge: eps is NaN")
+    if return_arg and reduce not in ("max", "min"):
+        raise ValueError("spmm_edge: return_arg is for max / min")
+    ct = _compute_dtype(X.dtype)
+    tv = None
+    if reduce == "softmax":
+        if torch.is_tensor(t):
+            if not t.is_floating_point():
+                raise TypeError(f"spmm_edge: t must be a float or a floating-point tensor, got {t.dtype}")
+            if t.dim() > 1 or (t.dim() == 1 and t.size(0) != h):
+                raise ValueError(f"spmm_edge: t must be a scalar or [{h}], got {tuple(t.shape)}")
+            tv = t.to(g.device, ct).expand(h).contiguous()   # autograd takes the gradient back to t's shape and dtype
+        else:
+            tv = torch.full((h,), float(t), dtype=ct, device=g.device)
+    home = X.device
+    Xd = X.to(g.device).contiguous()
+    Ed = E.to(g.device)
+    if Ed.stride(1) != 1 or (g.nnz > 1 and Ed.stride(0) < h):
+        Ed = Ed.contiguous()
+    if not fused:
+        out, arg = _edge_composed(g, Xd, Ed, tv, reduce, act, eps, bool(return_arg))
+    else:
+        out, arg = SpmmEdge.apply(g, Xd, Ed, tv, reduce, ACT_CODE[act], eps, bool(return_arg))
+    return (out.to(home), arg.to(home)) if return_arg else out.to(home)
+
+
+def matmul_edge(adj, B: torch.Tensor, E: torch.Tensor, reduce: str = "sum", act=None, eps: float = 0.0, t=1.0, fused: bool = True):
+    """``spmm_edge`` on the structure of a SparseTensor or a ``backend_pim`` wrapper (its stored values are not used: unit weights)"""
+    if getattr(adj, "row_sharded", False):
+        raise NotImplementedError("matmul_edge is not available on a RowShardAdj (one GPU only)")
+    return spmm_edge(EdgeGraph.of(adj), B, E, reduce, act, eps, t, fused=fused)

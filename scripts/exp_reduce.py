@@ -21,7 +21,16 @@ in one process, written to profiles/exp_softmax.txt (--out) as JSON lines:
   on products-mini the same beside the fused=False composition (X[col], edge_softmax and spmm_values with heads = h: it fits there),
     forward and forward + backward, with peak memory;
   the bytes the two workspace functions return.
-    python scripts/exp_reduce.py --section softmax [--iters 10] [--out profiles/exp_softmax.txt]"""
+    python scripts/exp_reduce.py --section softmax [--iters 10] [--out profiles/exp_softmax.txt]
+--section edge: messages with a feature-wide edge feature (pygim_spmm_edge, pygim_spmm_edge_softmax, pygim_spmm_edge_backward), float32 and
+bfloat16, sum and softmax, two rounds in one process, written to profiles/exp_edge_message.txt (--out) as JSON lines:
+  on the Reddit-shaped graph at --edge-h (default 32: E and dE are [nnz, h], 14.7 GB each in float32 there; at h = 256 one of them would
+    be 117 GB) and on products-mini at --h: the plain gather of the same fold (spmm_values with unit weights / spmm_softmax), the fused
+    forward relu(X[col] + E) + eps, the fused=False composition through the [nnz, h] message tensor, and forward + backward of both
+    (gradients of X, E and t), each with the peak of allocated memory; e_stream_tb_s is the rate of the E bytes alone;
+  with --parent-lib PATH (the parent commit's libpygim_hip.so loaded beside this build) the calls that existed before -- spmm_values,
+    spmm_reduce mean and max, spmm_softmax, each forward and forward + backward -- on both builds, alternating: the parity of what did not change.
+    python scripts/exp_reduce.py --section edge [--iters 10] [--edge-h 32] [--parent-lib PATH] [--out profiles/exp_edge_message.txt]"""
 import argparse
 import json
 import os
@@ -190,18 +199,161 @@ def section_softmax(args):
     torch.ops.pim_ops.dpu_release()
 
 
+class OtherBuild:
+    """another build of the library (the parent commit's libpygim_hip.so) loaded beside this one: inside ``with other:`` every call of
+    pygim_amd._lib goes to it, so the two builds are timed alternately in one process on the same tensors (as scripts/exp_attention.py does)"""
+    NAMES = ("pygim_init_ranks", "pygim_release", "pygim_last_error", "pygim_spmm_values", "pygim_spmm_values_workspace", "pygim_spmm_reduce",
+             "pygim_spmm_reduce_workspace", "pygim_spmm_reduce_backward", "pygim_sddmm", "pygim_spmm_softmax", "pygim_spmm_softmax_workspace", "pygim_spmm_softmax_backward",
+             "pygim_spmm_softmax_backward_workspace")
+
+    def __init__(self, path):
+        import ctypes
+
+        self.mine = _lib.lib()
+        self.handle = ctypes.CDLL(os.path.abspath(path))
+        for name in self.NAMES:
+            src, dst = getattr(self.mine, name), getattr(self.handle, name)
+            dst.argtypes, dst.restype = src.argtypes, src.restype
+        with self:
+            _lib.init_ranks(1)
+
+    def __enter__(self):
+        _lib._lib = self.handle
+
+    def __exit__(self, *exc):
+        _lib._lib = self.mine
+
+
+def section_edge(args):
+    dev = torch.device("cuda", 0)
+    iters = args.iters
+    pim_ops.load("spmm")
+    torch.ops.pim_ops.dpu_init_ranks(1)
+    parent = OtherBuild(args.parent_lib) if args.parent_lib else None
+    out_path = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exp_edge_message.txt")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    sink = open(out_path, "w")
+    eps = 1e-7
+
+    def peak(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        ms = timed(fn, reps)
+        return ms, (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20
+
+    for shape, h in (("reddit", args.edge_h), ("products-mini", args.h)):
+        n, nnz, d_max = synth.SHAPES[shape]
+        rowptr, col = synth.make_csr(n, nnz, d_max, seed=0, device=dev)
+        g = attention.EdgeGraph(rowptr, col, (n, n))
+        g.transposed()   # built once, outside the timings
+        g.entry_ids_t()
+
+        def line(**kw):
+            text = json.dumps({"graph": shape, "h": h, "nnz": nnz, **kw})
+            print(text, flush=True)
+            sink.write(text + "\n")
+            sink.flush()
+
+        ones = torch.ones(nnz, 1, device=dev)
+        for dtype, name in ((torch.float32, "float32"), (torch.bfloat16, "bfloat16")):
+            x = synth.features(n, h, torch.float32, seed=0, device=dev, kind="uniform").to(dtype)
+            G = synth.features(n, h, torch.float32, seed=1, device=dev, kind="uniform").to(dtype)
+            E = (torch.rand((nnz, h), device=dev, dtype=torch.float32) - 0.5).to(dtype)
+            tv = torch.linspace(0.5, 2.0, h, device=dev)
+            streamed = nnz * h * x.element_size()   # the bytes of E (and of dE); e_stream_tb_s counts these alone, not the gathered rows of X
+
+            def step(fold, fused):
+                xx, ee, tt = x.detach().requires_grad_(), E.detach().requires_grad_(), tv.detach().requires_grad_()
+                red.spmm_edge(g, xx, ee, fold, "relu", eps, tt, fused=fused).backward(G)
+                return xx.grad, ee.grad, tt.grad
+
+            for rnd in range(2):
+                for fold in ("sum", "softmax"):
+                    if fold == "sum":
+                        plain = timed(lambda: attention._run_spmm_values(g, ones, x, 1), iters)
+                    else:
+                        plain = timed(lambda: red._run_spmm_softmax(g, x, tv, False), iters)
+                    fused, f_mib = peak(lambda: red._run_spmm_edge(g, x, E, fold, 1, eps, tv, False, False), iters)
+                    with torch.no_grad():
+                        c_ms, c_mib = peak(lambda: red.spmm_edge(g, x, E, fold, "relu", eps, tv, fused=False), max(iters // 2, 1))
+                    fb_ms, fb_mib = peak(lambda: step(fold, True), max(iters // 2, 1))
+                    # the composed softmax backward is one sddmm per feature (h launches): one repetition
+                    cfb_ms, cfb_mib = peak(lambda: step(fold, False), 1 if fold == "softmax" else max(iters // 2, 1))
+                    line(fold=fold, dtype=name, round=rnd, plain_gather_ms=round(plain, 3), fused_forward_ms=round(fused, 3),
+                         fused_over_plain=round(fused / plain, 3), fused_forward_peak_mib=round(f_mib, 1), e_stream_tb_s=round(streamed / fused / 1e9, 2),
+                         composed_forward_ms=round(c_ms, 3), composed_forward_peak_mib=round(c_mib, 1), composed_forward_over_fused=round(c_ms / fused, 2),
+                         fused_fwd_bwd_ms=round(fb_ms, 3), fused_fwd_bwd_peak_mib=round(fb_mib, 1), composed_fwd_bwd_ms=round(cfb_ms, 3),
+                         composed_fwd_bwd_peak_mib=round(cfb_mib, 1), composed_fwd_bwd_over_fused=round(cfb_ms / fb_ms, 2),
+                         e_or_de_mib=round(streamed / 2 ** 20, 1))
+            for fold in ("sum", "softmax"):
+                (dx_f, de_f, dt_f), (dx_c, de_c, dt_c) = step(fold, True), step(fold, False)
+                rec = dict(dx_max_abs_fused_minus_composed=float((dx_f.float() - dx_c.float()).abs().max()), dx_max_abs=float(dx_c.float().abs().max()),
+                           de_max_abs_fused_minus_composed=float((de_f.float() - de_c.float()).abs().max()), de_max_abs=float(de_c.float().abs().max()))
+                if fold == "softmax":
+                    rec.update(dt_max_abs_fused_minus_composed=float((dt_f - dt_c).abs().max()), dt_max_abs=float(dt_c.abs().max()))
+                line(what="gradient check", fold=fold, dtype=name, **rec)
+                del dx_f, de_f, dx_c, de_c
+            del E
+            torch.cuda.empty_cache()
+            if parent is not None:   # what existed before, this build and the parent's alternately
+                def sm_step():
+                    xx, tt = x.detach().requires_grad_(), tv.detach().requires_grad_()
+                    red.spmm_softmax(g, xx, tt).backward(G)
+
+                def grad_step(fn):
+                    def run():
+                        xx = x.detach().requires_grad_()
+                        fn(xx).backward(G)
+                    return run
+
+                calls = {"spmm_values": lambda: attention._run_spmm_values(g, ones, x, 1),
+                         "spmm_values_fwd_bwd": grad_step(lambda xx: attention.spmm_values(g, ones, xx)),
+                         "spmm_reduce_mean_fwd_bwd": grad_step(lambda xx: red.spmm_reduce(g, xx, "mean")),
+                         "spmm_reduce_mean": lambda: red._run_spmm_reduce(g, None, x, red.REDUCE_CODE["mean"], False),
+                         "spmm_softmax": lambda: red._run_spmm_softmax(g, x, tv, True), "spmm_softmax_fwd_bwd": sm_step}
+                if dtype == torch.float32:
+                    calls["spmm_reduce_max_arg"] = lambda: red._run_spmm_reduce(g, None, x, red.REDUCE_CODE["max"], True)
+                    calls["spmm_reduce_max_fwd_bwd"] = grad_step(lambda xx: red.spmm_reduce(g, xx, "max"))
+                for rnd in range(2):
+                    rec = {}
+                    for key, fn in calls.items():
+                        with parent:
+                            a = timed(fn, iters)
+                        b = timed(fn, iters)
+                        with parent:
+                            a2 = timed(fn, iters)
+                        b2 = timed(fn, iters)
+                        rec[key] = dict(parent_ms=[round(a, 3), round(a2, 3)], this_ms=[round(b, 3), round(b2, 3)],
+                                        this_over_parent=round((b + b2) / (a + a2), 4))
+                    line(what="parity with the parent build", dtype=name, round=rnd, **rec)
+            del x, G
+        del g, ones, rowptr, col
+        torch.cuda.empty_cache()
+    sink.close()
+    if parent is not None:
+        with parent:
+            _lib.release()
+    torch.ops.pim_ops.dpu_release()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--shape", default="reddit")
-    ap.add_argument("--section", default="reduce", choices=("reduce", "multi", "softmax"))
+    ap.add_argument("--section", default="reduce", choices=("reduce", "multi", "softmax", "edge"))
+    ap.add_argument("--edge-h", type=int, default=32, help="--section edge: the width on the Reddit-shaped graph (E and dE are [nnz, h])")
+    ap.add_argument("--parent-lib", default=None, help="--section edge: the parent commit's libpygim_hip.so, timed beside this build")
     ap.add_argument("--out", default=None, help="--section multi / softmax: where the JSON lines go (default profiles/exp_multi_reduce.txt / exp_softmax.txt)")
     args = ap.parse_args()
     if args.section == "multi":
         return section_multi(args)
     if args.section == "softmax":
         return section_softmax(args)
+    if args.section == "edge":
+        return section_edge(args)
     dev = torch.device("cuda", 0)
     n, nnz, d_max = synth.SHAPES[args.shape]
     h, iters = args.h, args.iters
