@@ -24,6 +24,8 @@
 #include "lds_form.hpp"
 #include "lds_launch.hpp"
 #include "run_plan.hpp"
+#include "sweep_plan.hpp"
+#include "group_args.hpp"
 #include "transpose_dev.hpp"
 #include "sddmm_dev.hpp"
 #include "row_gather_dev.hpp"
@@ -231,12 +233,9 @@ static int group_create(int format, int dtype, int n_parts, const int32_t *const
         if (values && values[0]) (void)hipFree(const_cast<void *>(values[0]));
     };
     if (int rc = need_init()) return drop_adopted(), rc;
-    if (format != PYGIM_CSR && format != PYGIM_COO) return fail(PYGIM_ERR_INVALID, "format must be CSR(0) or COO(1)");
     const size_t es = dtype_size(dtype);
-    if (es == 0) return fail(PYGIM_ERR_INVALID, "unknown dtype");
-    if (n_parts <= 0 || !idx0 || !colind || !nrows || !ncols || !nnz || !n_dense || !dense_cols || !out_handle)
-        return fail(PYGIM_ERR_INVALID, "null argument or n_parts <= 0");
-    if (h_size <= 0) return fail(PYGIM_ERR_INVALID, "h_size must be positive");
+    const ArgError bad = check_group_args(format, es, n_parts, idx0, colind, nrows, ncols, nnz, n_dense, dense_cols, h_size, out_handle);   // (group_args.hpp)
+    if (bad.code) return drop_adopted(), fail(bad.code, bad.text);
     const double t0 = now_ms();
     Group *g = new Group;
     g->format = format;
@@ -265,23 +264,9 @@ static int group_create(int format, int dtype, int n_parts, const int32_t *const
         p.nrows = nrows[i];
         p.ncols = ncols[i];
         p.nnz = nnz[i];
-        if (p.nrows != g->total_rows) return bail(fail(PYGIM_ERR_INVALID, "all sparse parts must have the same number of rows"));
-        if (p.nrows < 0 || p.ncols < 0 || p.nnz < 0 || p.nnz > 0xFFFFFFFFll || p.nrows >= 0xFFFFFFFFll ||
-            p.ncols > 0xFFFFFFFFll)
-            return bail(fail(PYGIM_ERR_INVALID, "part sizes must fit 32-bit indices (the reference's uint32 matrices)"));
-        if (n_dense[i] <= 0) return bail(fail(PYGIM_ERR_INVALID, "n_dense must be positive"));
-        int64_t sum = 0;
-        for (int64_t j = 0; j < n_dense[i]; j++) {
-            if (dense_cols[dpos + j] < 0) return bail(fail(PYGIM_ERR_INVALID, "negative dense width"));
-            p.dense_cols.push_back(dense_cols[dpos + j]);
-            sum += dense_cols[dpos + j];
-        }
+        p.dense_cols.assign(dense_cols + dpos, dense_cols + dpos + (size_t)n_dense[i]);
         dpos += (size_t)n_dense[i];
-        if (sum != h_size) return bail(fail(PYGIM_ERR_INVALID, "dense widths of a part must add up to h_size"));
         g->total_cols += p.ncols;
-        if (!idx0[i] && (format == PYGIM_CSR || p.nnz > 0)) return bail(fail(PYGIM_ERR_INVALID, "null index array"));
-        if (!colind[i] && p.nnz > 0) return bail(fail(PYGIM_ERR_INVALID, "null colind"));
-
         if ((rc = to_device<uint32_t>(colind[i], (size_t)p.nnz * 4, &p.colind, &p.own_colind, st))) return bail(rc);
         const void *v = values ? values[i] : nullptr;
         if (v) {
@@ -325,11 +310,7 @@ static int group_create(int format, int dtype, int n_parts, const int32_t *const
     int flags[4] = {0, 0, 0, 0};
     if (hipMemcpy(flags, g->d_flags, sizeof(flags), hipMemcpyDeviceToHost) != hipSuccess)
         return bail(fail(PYGIM_ERR_HIP, std::string("group validation: ") + hipGetErrorString(hipGetLastError())));
-    if (flags[1]) return bail(fail(PYGIM_ERR_INVALID, "index out of range in a sparse part"));
-    if (flags[0]) {
-        if (format == PYGIM_COO) return bail(fail(PYGIM_ERR_UNSORTED, "COO row indices are not sorted (pass a coalesced tensor)"));
-        return bail(fail(PYGIM_ERR_INVALID, "rowptr is not a non-decreasing prefix array ending at nnz"));
-    }
+    if (const ArgError inv = group_validation_error(format, flags); inv.code) return bail(fail(inv.code, inv.text));
     g->all_ones = (flags[2] == 0);
     // several sparse parts: also one merged matrix (built from the parts as given, before values are dropped or split)
     if (n_parts > 1 && g_tune.merge_parts && (rc = build_merged(g, es, st))) return bail(rc);
@@ -372,30 +353,13 @@ int pygim_group_create_transposed(int format, int dtype, int n_parts, const int3
                                   const int32_t *const *colind, const void *const *values, const int64_t *nrows,
                                   const int64_t *ncols, const int64_t *nnz, const int64_t *n_dense,
                                   const int64_t *dense_cols, int64_t h_size, int64_t *out_handle) {
-    // the argument checks of pygim_group_create, then its validation kernels on the input as given
+    // the argument checks of pygim_group_create (group_args.hpp), then its validation kernels on the input as given
     if (int rc = need_init()) return rc;
-    if (format != PYGIM_CSR && format != PYGIM_COO) return fail(PYGIM_ERR_INVALID, "format must be CSR(0) or COO(1)");
     const size_t es = dtype_size(dtype);
-    if (es == 0) return fail(PYGIM_ERR_INVALID, "unknown dtype");
-    if (n_parts <= 0 || !idx0 || !colind || !nrows || !ncols || !nnz || !n_dense || !dense_cols || !out_handle)
-        return fail(PYGIM_ERR_INVALID, "null argument or n_parts <= 0");
-    if (h_size <= 0) return fail(PYGIM_ERR_INVALID, "h_size must be positive");
+    const ArgError bad = check_group_args(format, es, n_parts, idx0, colind, nrows, ncols, nnz, n_dense, dense_cols, h_size, out_handle);
+    if (bad.code) return fail(bad.code, bad.text);
     uint64_t total_cols = 0, total_nnz = 0;
-    size_t dpos = 0;
     for (int i = 0; i < n_parts; i++) {
-        if (nrows[i] != nrows[0]) return fail(PYGIM_ERR_INVALID, "all sparse parts must have the same number of rows");
-        if (nrows[i] < 0 || ncols[i] < 0 || nnz[i] < 0 || nnz[i] > 0xFFFFFFFFll || nrows[i] >= 0xFFFFFFFFll || ncols[i] > 0xFFFFFFFFll)
-            return fail(PYGIM_ERR_INVALID, "part sizes must fit 32-bit indices (the reference's uint32 matrices)");
-        if (n_dense[i] <= 0) return fail(PYGIM_ERR_INVALID, "n_dense must be positive");
-        int64_t sum = 0;
-        for (int64_t j = 0; j < n_dense[i]; j++) {
-            if (dense_cols[dpos + j] < 0) return fail(PYGIM_ERR_INVALID, "negative dense width");
-            sum += dense_cols[dpos + j];
-        }
-        dpos += (size_t)n_dense[i];
-        if (sum != h_size) return fail(PYGIM_ERR_INVALID, "dense widths of a part must add up to h_size");
-        if (!idx0[i] && (format == PYGIM_CSR || nnz[i] > 0)) return fail(PYGIM_ERR_INVALID, "null index array");
-        if (!colind[i] && nnz[i] > 0) return fail(PYGIM_ERR_INVALID, "null colind");
         total_cols += (uint64_t)ncols[i];
         total_nnz += (uint64_t)nnz[i];
     }
@@ -454,11 +418,7 @@ int pygim_group_create_transposed(int format, int dtype, int n_parts, const int3
     int flags[4] = {0, 0, 0, 0};
     if (hipMemcpy(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost) != hipSuccess)
         return bail(fail(PYGIM_ERR_HIP, std::string("group validation: ") + hipGetErrorString(hipGetLastError())));
-    if (flags[1]) return bail(fail(PYGIM_ERR_INVALID, "index out of range in a sparse part"));
-    if (flags[0]) {
-        if (format == PYGIM_COO) return bail(fail(PYGIM_ERR_UNSORTED, "COO row indices are not sorted (pass a coalesced tensor)"));
-        return bail(fail(PYGIM_ERR_INVALID, "rowptr is not a non-decreasing prefix array ending at nnz"));
-    }
+    if (const ArgError inv = group_validation_error(format, flags); inv.code) return bail(fail(inv.code, inv.text));
     // the transpose (transpose_dev.hpp), then the creation path of any group: unit weights, plans, code streams and fallbacks as usual
     uint32_t *rowptrT = nullptr, *colT = nullptr;
     void *valsT = nullptr;

@@ -39,8 +39,7 @@ struct KernelTimer {
 template <typename T>
 bool want_panel(const Part &p, uint32_t w, int64_t ldx) {
     if (p.d_items == nullptr || g_tune.panel_mode == 2 || p.nrows == 0 || w == 0) return false;
-    if (g_tune.panel_mode == 0 && !(p.npanels == 1 || (double)p.nnz / ((double)p.nrows * p.npanels) >= (double)g_tune.panel_min_seg))
-        return false;
+    if (g_tune.panel_mode == 0 && !panels_pay(p.nnz, p.nrows, p.npanels, g_tune.panel_min_seg)) return false;   // (sweep_plan.hpp: the builder's rule)
     constexpr uint32_t V = 16 / sizeof(T), F = V * 8;
     const uint32_t nslices = (w + F - 1) / F;
     const bool tail_inside = (w % V) == 0;  // no partial 16-byte piece: nothing is read past a row's width

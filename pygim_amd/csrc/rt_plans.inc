@@ -1,35 +1,10 @@
 // rt_plans.inc -- part of pygim_hip.hip (inside its anonymous namespace): the one-time plans of a part -- long rows, the sweep's panels and work items
-// (locality order), which rows are alike (find_similarity), the LDS-staged plan and its code stream (generated on the device, lds_codegen_dev.hpp; the host
+// (decided in sweep_plan.hpp, built here), which rows are alike (find_similarity), the LDS-staged plan and its code stream (generated on the device, lds_codegen_dev.hpp; the host
 // encoder as checker and rung below).  The reference's counterpart: prepare_pim_csr / partition walks, spmm_default/spmm_mul_csr.c:118-330.
 template <typename T> void launch_check_ones(const void *v, uint32_t n, int *flag, hipStream_t st) {
     hipLaunchKernelGGL((k_check_ones<T>), dim3((n + 255) / 256), dim3(256), 0, st, (const T *)v, n, flag);
 }
 
-// Long-row plan from a host copy of rowptr: rows above the threshold are cut
-// into segments of `thresh` entries.
-void plan_long_rows(const uint32_t *rowptr, int64_t nrows, uint32_t thresh, uint32_t seg, const std::vector<char> *flags,
-                    std::vector<uint32_t> &tasks, std::vector<uint32_t> &desc) {
-    // a row is long when it has more than `thresh` entries, or -- when flags are given -- when flagged
-    for (int64_t r = 0; r < nrows; r++) {
-        const uint32_t s = rowptr[r], e = rowptr[r + 1];
-        const bool is_long = flags ? (*flags)[(size_t)r] != 0 : (e - s > thresh);
-        if (!is_long || e == s) continue;
-        const uint32_t first = (uint32_t)(tasks.size() / 3);
-        uint32_t n = 0;
-        for (uint32_t a = s; a < e; a += seg, n++) {
-            tasks.push_back((uint32_t)r);
-            tasks.push_back(a);
-            tasks.push_back(std::min(e, a + seg));
-        }
-        desc.push_back((uint32_t)r);
-        desc.push_back(first);
-        desc.push_back(n);
-    }
-}
-
-// One-time plans of a part (needs its row pointers on the host): the long-row segment plans and the
-// L2-blocked panel plan.  Replaces the reference's prepare_pim_csr/prepare_pim_coo balancing
-// (spmm_mul_csr.c:118-259) -- same purpose, different machine.
 int build_lds_plan(Part &p, size_t es, int *d_flag_sorted, hipStream_t st, const std::vector<uint32_t> &h_rowptr, int64_t h_hint);
 double now_ms();
 static thread_local int t_plan_dtype = -1;   // element type of the group being created (the plan builders see the element SIZE only)
@@ -72,181 +47,108 @@ static void find_similarity(Part &p, hipStream_t st, bool force_lp) {
                 (long long)p.nrows, p.sim_why.empty() ? "" : " -- ", p.sim_why.c_str(), now_ms() - t0);
 }
 
+// The tunables the sweep's plan reads (sweep_plan.hpp), copied in this one place.
+static SweepKnobs sweep_knobs() {
+    SweepKnobs k;
+#define PYGIM_KNOB(name) k.name = g_tune.name
+    PYGIM_KNOB(panel_mode); PYGIM_KNOB(panel_bytes); PYGIM_KNOB(panel_min_seg); PYGIM_KNOB(panel_coop); PYGIM_KNOB(panel_locality); PYGIM_KNOB(panel_col16);
+    PYGIM_KNOB(vec_lds); PYGIM_KNOB(vec_kernel); PYGIM_KNOB(long_row_threshold); PYGIM_KNOB(long_segment);
+#undef PYGIM_KNOB
+    return k;
+}
+
+// One long-row plan (sweep_plan.hpp plan_long_rows) and its two tables on the device.
+static bool upload_long_plan(LongPlan &lp, const std::vector<uint32_t> &h_rowptr, uint32_t thresh, const std::vector<char> *flags, const SweepKnobs &k) {
+    lp.thresh = thresh;
+    std::vector<uint32_t> tasks, desc;
+    plan_long_rows(h_rowptr.data(), (int64_t)h_rowptr.size() - 1, thresh, long_row_segment(thresh, k), flags, tasks, desc);
+    lp.n_tasks = (uint32_t)(tasks.size() / 3);
+    lp.n_long = (uint32_t)(desc.size() / 3);
+    if (!lp.n_tasks) return true;
+    return hipMalloc((void **)&lp.d_tasks, tasks.size() * 4) == hipSuccess &&
+           hipMalloc((void **)&lp.d_desc, desc.size() * 4) == hipSuccess &&
+           hipMemcpy(lp.d_tasks, tasks.data(), tasks.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(lp.d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// Does every row store its column ids in order?  The answer stays with the part (cols_sorted).
+static int check_cols_sorted(Part &p, int *d_flag_sorted, hipStream_t st) {
+    int unsorted = 0;
+    if (hipMemsetAsync(d_flag_sorted, 0, sizeof(int), st) != hipSuccess) return fail(PYGIM_ERR_HIP, "flag reset");
+    hipLaunchKernelGGL(k_check_sorted_cols, dim3((unsigned)((p.nrows + 255) / 256)), dim3(256), 0, st, p.rowptr, p.colind, (uint32_t)p.nrows, d_flag_sorted);
+    if (hipMemcpy(&unsorted, d_flag_sorted, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(PYGIM_ERR_HIP, "sortedness check");
+    p.cols_sorted = unsorted ? 0 : 1;
+    return 0;
+}
+
+// Panel pointers of every row: binary searches on the device for several panels, the row pointers for one.
+static int panel_pointers(const Part &p, uint32_t npan, uint32_t panel_cols, const std::vector<uint32_t> &h_rowptr, hipStream_t st, std::vector<uint32_t> &pp) {
+    if (npan == 1) {
+        pp = one_panel_pointers(h_rowptr.data(), (size_t)p.nrows);
+        return 0;
+    }
+    const size_t pp_elems = (size_t)(npan + 1) * (size_t)p.nrows;
+    pp.resize(pp_elems);
+    uint32_t *d_pp = nullptr;
+    if (hipMalloc((void **)&d_pp, pp_elems * 4) != hipSuccess) return fail(PYGIM_ERR_HIP, "panel pointers");
+    hipLaunchKernelGGL(k_build_panel_ptr, dim3((unsigned)((pp_elems + 255) / 256)), dim3(256), 0, st, (const uint32_t *)nullptr, p.rowptr, p.colind, (uint32_t)p.nrows, npan,
+                       panel_cols, d_pp);
+    const hipError_t ce = hipMemcpy(pp.data(), d_pp, pp_elems * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_pp);
+    return ce == hipSuccess ? 0 : fail(PYGIM_ERR_HIP, "panel pointers D2H");
+}
+
+// The one place that writes a planned sweep into its part: the tables on the host, the three item arrays and the 16-bit column ids on the device.
+static int adopt_sweep_plan(Part &p, uint32_t npan, uint32_t panel_cols, SweepItems &it, bool locality, const SweepKnobs &k, hipStream_t st) {
+    p.npanels = npan;
+    p.panel_cols = panel_cols;
+    p.panel_locality_used = locality;
+    p.n_items = it.rows.size();
+    p.panel_off = std::move(it.panel_off);
+    p.panel_coop = std::move(it.panel_coop);
+    p.panel_long128 = std::move(it.panel_long128);
+    p.panel_nnz = std::move(it.panel_nnz);
+    if (!p.n_items) return 0;
+    if (hipMalloc((void **)&p.d_items, 3 * p.n_items * 4) != hipSuccess ||
+        hipMemcpy(p.d_items, it.rows.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_items + p.n_items, it.beg.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p.d_items + 2 * p.n_items, it.lens.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(PYGIM_ERR_HIP, "panel plan upload");
+    if (!sweep_wants_col16(k, panel_cols, p.nnz, p.n_items)) return 0;
+    if (hipMalloc((void **)&p.col16, sweep_col16_bytes(p.nnz)) != hipSuccess) return fail(PYGIM_ERR_HIP, "col16 alloc");
+    hipLaunchKernelGGL(k_make_col16, dim3((unsigned)((p.nnz + 255) / 256)), dim3(256), 0, st, p.colind, (uint64_t)p.nnz, panel_cols, p.col16);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(PYGIM_ERR_HIP, "col16 build");
+    return 0;
+}
+
+// One-time plans of a part: the long-row segment plans and the L2-blocked panel plan.  Replaces the reference's prepare_pim_csr / prepare_pim_coo
+// balancing (spmm_mul_csr.c:118-259) -- same purpose, different machine.  What the plans hold is decided in sweep_plan.hpp, without a device; here is
+// what needs one, in the order it always had: the row pointers down,
+// the long-row plan up, the sortedness question, the panel pointers, the heavy rows' plan up, which rows are alike, the items up, the 16-bit ids.
 int build_plans(Part &p, size_t es, int *d_flag_sorted, hipStream_t st, int64_t h_hint = 0, bool allow_lds = true) {
     std::vector<uint32_t> h_rowptr((size_t)p.nrows + 1);
     if (hipMemcpy(h_rowptr.data(), p.rowptr, h_rowptr.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(PYGIM_ERR_HIP, "rowptr D2H");
-    auto build_long = [&](LongPlan &lp, uint32_t thresh, const std::vector<char> *flags) -> bool {
-        lp.thresh = thresh;
-        std::vector<uint32_t> tasks, desc;
-        const uint32_t seg = (uint32_t)std::min<int64_t>(thresh, std::max<int64_t>(64, g_tune.long_segment));
-        plan_long_rows(h_rowptr.data(), p.nrows, thresh, seg, flags, tasks, desc);
-        lp.n_tasks = (uint32_t)(tasks.size() / 3);
-        lp.n_long = (uint32_t)(desc.size() / 3);
-        if (!lp.n_tasks) return true;
-        return hipMalloc((void **)&lp.d_tasks, tasks.size() * 4) == hipSuccess &&
-               hipMalloc((void **)&lp.d_desc, desc.size() * 4) == hipSuccess &&
-               hipMemcpy(lp.d_tasks, tasks.data(), tasks.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-               hipMemcpy(lp.d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    const uint32_t base_thresh = (uint32_t)std::min<int64_t>(0x7FFFFFFF, std::max<int64_t>(64, g_tune.long_row_threshold));
-    if (!build_long(p.lp_base, base_thresh, nullptr)) return fail(PYGIM_ERR_HIP, "long-row plan upload");
-    // L2-blocked plan: columns cut into panels whose 128-byte feature slice fits the L2 budget,
-    // per panel the length-sorted list of work items
-    if (g_tune.panel_mode != 2 && p.nrows > 0 && p.nnz > 0) {
-        int64_t budget_rows = std::max<int64_t>(1, g_tune.panel_bytes / 128);
-        // groups whose rows of X hold at most 4 elements never take the wide sweep: their panels are sized for the LDS-staged
-        // SpMV kernel instead (a panel of X, h elements per column, inside 128 KiB of a workgroup's LDS; the rest parks results)
-        if (h_hint >= 1 && h_hint <= 4 && g_tune.vec_lds && g_tune.vec_kernel)
-            budget_rows = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(budget_rows, 65536),  // (16-bit panel-local ids)
-                                                                 (int64_t)((128 * 1024 - 64) / ((size_t)h_hint * es))));
-        uint32_t npan = (uint32_t)std::max<int64_t>(1, (p.ncols + budget_rows - 1) / budget_rows);
-        bool worth = g_tune.panel_mode == 1 || npan == 1 ||
-                     (double)p.nnz / ((double)p.nrows * npan) >= (double)g_tune.panel_min_seg;
-        if (npan > 1 && worth) {
-            // column panels are cut by binary search inside each row: the rows must hold sorted column ids
-            // (torch_sparse / coalesce() deliver them sorted); otherwise fall back to one panel
-            int unsorted = 0;
-            if (hipMemsetAsync(d_flag_sorted, 0, sizeof(int), st) != hipSuccess) return fail(PYGIM_ERR_HIP, "flag reset");
-            hipLaunchKernelGGL(k_check_sorted_cols, dim3((unsigned)((p.nrows + 255) / 256)), dim3(256), 0, st, p.rowptr,
-                               p.colind, (uint32_t)p.nrows, d_flag_sorted);
-            if (hipMemcpy(&unsorted, d_flag_sorted, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(PYGIM_ERR_HIP, "sortedness check");
-            p.cols_sorted = unsorted ? 0 : 1;
-            if (unsorted) worth = false;
+    const SweepKnobs k = sweep_knobs();
+    const uint32_t base_thresh = long_row_base_threshold(k);
+    if (!upload_long_plan(p.lp_base, h_rowptr, base_thresh, nullptr, k)) return fail(PYGIM_ERR_HIP, "long-row plan upload");
+    const SweepPanels want = sweep_panel_count(p.nrows, p.ncols, p.nnz, es, h_hint, k);
+    if (want.plan) {
+        if (want.ask_sorted)
+            if (int rc = check_cols_sorted(p, d_flag_sorted, st)) return rc;
+        const uint32_t npan = sweep_panels_given(want, p.cols_sorted == 0), panel_cols = sweep_panel_cols(p.ncols, npan);
+        const size_t nr = (size_t)p.nrows;
+        std::vector<uint32_t> pp;
+        if (int rc = panel_pointers(p, npan, panel_cols, h_rowptr, st, pp)) return rc;
+        const std::vector<char> heavy = sweep_heavy_rows(pp.data(), nr, npan, base_thresh);
+        if (!upload_long_plan(p.lp_panel, h_rowptr, base_thresh, &heavy, k)) return fail(PYGIM_ERR_HIP, "long-row plan upload");
+        std::vector<uint32_t> rank;
+        if (sweep_wants_similarity(k, h_hint, p.is_extra, p.sim_kind)) {
+            find_similarity(p, st, k.panel_locality == 2);   // (2: propagation whatever the size -- tests)
+            rank = sweep_locality_rank(p.sim_kind, p.sim_order, nr);
         }
-        if (!worth) {
-            // too few entries per (row, panel) for L2 blocking: ONE panel.  The sweep's other half --
-            // length-sorted items, 32-id column chunks, line-sized gathers from the slice-major copy, wave-
-            // cooperative long rows -- still beats whole-row gathers (products-shaped, X = 2.5 GB:
-            // 23.8 ms against 28.6 ms for k_csr_wide)
-            npan = 1;
-            worth = true;
-        }
-        if (worth) {
-            p.npanels = npan;
-            p.panel_cols = (uint32_t)((p.ncols + npan - 1) / npan);
-            // panel pointers of every row (device binary searches), then the lists on the host
-            const size_t pp_elems = (size_t)(npan + 1) * (size_t)p.nrows;
-            std::vector<uint32_t> pp(pp_elems);
-            if (npan == 1) {
-                std::copy(h_rowptr.begin(), h_rowptr.end() - 1, pp.begin());
-                std::copy(h_rowptr.begin() + 1, h_rowptr.end(), pp.begin() + p.nrows);
-            } else {
-                uint32_t *d_pp = nullptr;
-                if (hipMalloc((void **)&d_pp, pp_elems * 4) != hipSuccess) return fail(PYGIM_ERR_HIP, "panel pointers");
-                hipLaunchKernelGGL(k_build_panel_ptr, dim3((unsigned)((pp_elems + 255) / 256)), dim3(256), 0, st,
-                                   (const uint32_t *)nullptr, p.rowptr, p.colind, (uint32_t)p.nrows, npan, p.panel_cols, d_pp);
-                const hipError_t ce = hipMemcpy(pp.data(), d_pp, pp_elems * 4, hipMemcpyDeviceToHost);
-                (void)hipFree(d_pp);
-                if (ce != hipSuccess) return fail(PYGIM_ERR_HIP, "panel pointers D2H");
-            }
-            const uint32_t *rp = h_rowptr.data();
-            const size_t nr = (size_t)p.nrows;
-            // rows whose share of ONE panel is enormous (16x the long-row threshold) leave the sweep for
-            // the segment kernels; merely long items stay and are walked by a whole wave (panel_coop)
-            std::vector<char> heavy(nr, 0);
-            for (uint32_t q = 0; q < npan; q++) {
-                const uint32_t *lo = pp.data() + (size_t)q * nr, *hi = lo + nr;
-                for (size_t r = 0; r < nr; r++)
-                    if ((uint64_t)(hi[r] - lo[r]) > (uint64_t)base_thresh * 16) heavy[r] = 1;
-            }
-            if (!build_long(p.lp_panel, base_thresh, &heavy)) return fail(PYGIM_ERR_HIP, "long-row plan upload");
-            std::vector<uint32_t> rows_v, beg_v, len_v, order;
-            // rank of every row in the locality order (empty = items by length alone): the SpMV end keeps its length classes
-            std::vector<uint32_t> loc_rank;
-            // (the sparse half of a density split adds into C like a correction part -- is_extra -- but brings its parent's order along)
-            if (g_tune.panel_locality && !(h_hint >= 1 && h_hint <= 4) && (!p.is_extra || p.sim_kind == 2)) {
-                find_similarity(p, st, g_tune.panel_locality == 2);   // (2: propagation whatever the size -- tests)
-                if (p.sim_kind == 1) {
-                    loc_rank.resize(nr);
-                    for (size_t r = 0; r < nr; r++) loc_rank[r] = (uint32_t)r;
-                } else if (p.sim_kind == 2) {
-                    loc_rank.resize(nr);
-                    for (size_t k = 0; k < nr; k++) loc_rank[p.sim_order[k]] = (uint32_t)k;
-                }
-                p.panel_locality_used = !loc_rank.empty();
-            }
-            p.panel_off.assign(1, 0);
-            p.panel_coop.clear();
-            p.panel_long128.clear();
-            p.panel_nnz.clear();
-            const uint32_t coop_cap = (uint32_t)std::max<int64_t>(64, g_tune.panel_coop);
-            for (uint32_t q = 0; q < npan; q++) {
-                const uint32_t *lo = pp.data() + (size_t)q * nr, *hi = lo + nr;
-                order.clear();
-                for (size_t r = 0; r < nr; r++) {
-                    const uint32_t deg = rp[r + 1] - rp[r];
-                    if (heavy[r]) continue;                          // segment kernels
-                    // (empty rows are items of panel 0: they zero their row of C; a correction part only ever adds, so it has none)
-                    if (hi[r] > lo[r] || (q == 0 && deg == 0 && !p.is_extra)) order.push_back((uint32_t)r);
-                }
-                {   // stable counting sort by item length, longest first (O(items + longest))
-                    uint32_t longest = 0;
-                    for (uint32_t r : order) longest = std::max(longest, hi[r] - lo[r]);
-                    std::vector<size_t> start((size_t)longest + 2, 0);
-                    for (uint32_t r : order) start[(size_t)(longest - (hi[r] - lo[r])) + 1]++;
-                    for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
-                    std::vector<uint32_t> sorted(order.size());
-                    for (uint32_t r : order) sorted[start[(size_t)(longest - (hi[r] - lo[r]))]++] = r;
-                    order.swap(sorted);
-                }
-                uint32_t nco = 0;
-                for (uint32_t r : order) nco += (hi[r] - lo[r] > coop_cap) ? 1u : 0u;  // sorted: a prefix
-                if (!loc_rank.empty() && order.size() > nco) {
-                    // LOCALITY order (round 5) behind the wave-cooperative prefix: blocks of 2048 rows of the similarity (or id) order,
-                    // longest first inside a block (a stable counting sort by block of the length-sorted list).  Workgroups that run side
-                    // by side on an XCD then gather the same community's rows of X out of its L2 instead of 8 x 32 unrelated ones
-                    const uint32_t nblk = (uint32_t)((nr + 2047) / 2048);
-                    std::vector<size_t> bstart((size_t)nblk + 1, 0);
-                    for (size_t k = nco; k < order.size(); k++) bstart[(size_t)(loc_rank[order[k]] >> 11) + 1]++;
-                    for (size_t k = 1; k < bstart.size(); k++) bstart[k] += bstart[k - 1];
-                    std::vector<uint32_t> byblk(order.size() - nco);
-                    for (size_t k = nco; k < order.size(); k++) byblk[bstart[loc_rank[order[k]] >> 11]++] = order[k];
-                    std::copy(byblk.begin(), byblk.end(), order.begin() + nco);
-                }
-                p.panel_coop.push_back(nco);
-                uint32_t n256 = 0, n128 = 0, n64 = 0, n32 = 0;
-                uint64_t pn = 0;
-                for (uint32_t r : order) {
-                    const uint32_t l = hi[r] - lo[r];
-                    n256 += l > 256u ? 1u : 0u;  // sorted: prefixes
-                    n128 += l > 128u ? 1u : 0u;
-                    n64 += l > 64u ? 1u : 0u;
-                    n32 += l > 32u ? 1u : 0u;
-                    pn += l;
-                }
-                p.panel_long128.push_back(n256);
-                p.panel_long128.push_back(n128);
-                p.panel_long128.push_back(n64);
-                p.panel_long128.push_back(n32);
-                p.panel_nnz.push_back(pn);
-                for (uint32_t r : order) {
-                    rows_v.push_back(r);
-                    beg_v.push_back(lo[r]);
-                    const uint32_t first = (lo[r] == rp[r]) ? 0x80000000u : 0u;     // no entries in earlier panels
-                    const uint32_t last = (hi[r] == rp[r + 1]) ? 0x40000000u : 0u;  // none in later panels
-                    len_v.push_back((hi[r] - lo[r]) | first | last);
-                }
-                p.panel_off.push_back(rows_v.size());
-            }
-            p.n_items = rows_v.size();
-            if (p.n_items > 0) {
-                if (hipMalloc((void **)&p.d_items, 3 * p.n_items * 4) != hipSuccess ||
-                    hipMemcpy(p.d_items, rows_v.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(p.d_items + p.n_items, beg_v.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(p.d_items + 2 * p.n_items, len_v.data(), p.n_items * 4, hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(PYGIM_ERR_HIP, "panel plan upload");
-                // 16-bit panel-local column ids (2 bytes per entry more, half the index bytes per sweep)
-                if (g_tune.panel_col16 && p.panel_cols <= 65536 && p.nnz > 0) {
-                    // (+ 64 bytes: the LDS-staged SpMV kernel fetches ids four at a time and may read past the last entry)
-                    if (hipMalloc((void **)&p.col16, (size_t)p.nnz * 2 + 64) != hipSuccess) return fail(PYGIM_ERR_HIP, "col16 alloc");
-                    hipLaunchKernelGGL(k_make_col16, dim3((unsigned)((p.nnz + 255) / 256)), dim3(256), 0, st, p.colind,
-                                       (uint64_t)p.nnz, p.panel_cols, p.col16);
-                    if (hipStreamSynchronize(st) != hipSuccess) return fail(PYGIM_ERR_HIP, "col16 build");
-                }
-            }
-        }
+        SweepItems items = sweep_items(h_rowptr.data(), pp.data(), nr, npan, heavy, rank, p.is_extra, sweep_coop_cap(k));
+        if (int rc = adopt_sweep_plan(p, npan, panel_cols, items, !rank.empty(), k, st)) return rc;
     }
     // (the column blocks of a group that also has its merged matrix run through the merged plan: no second token stream for them)
     return allow_lds ? build_lds_plan(p, es, d_flag_sorted, st, h_rowptr, h_hint) : 0;
@@ -753,14 +655,8 @@ static int build_lds_plan_form(Part &p, size_t val_es, int *d_flag_sorted, hipSt
     in.k.l16_batch = LDS_L16_BATCH;
     const LdsForm f = lds_choose_form(in, lds_form_knobs());
     if (!f.plan) return 0;
-    if (p.cols_sorted < 0) {  // (the panel plan may have asked already)
-        int unsorted = 0;
-        if (hipMemsetAsync(d_flag_sorted, 0, sizeof(int), st) != hipSuccess) return fail(PYGIM_ERR_HIP, "flag reset");
-        hipLaunchKernelGGL(k_check_sorted_cols, dim3((unsigned)((p.nrows + 255) / 256)), dim3(256), 0, st, p.rowptr, p.colind,
-                           (uint32_t)p.nrows, d_flag_sorted);
-        if (hipMemcpy(&unsorted, d_flag_sorted, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(PYGIM_ERR_HIP, "sortedness check");
-        p.cols_sorted = unsorted ? 0 : 1;
-    }
+    if (p.cols_sorted < 0)   // (the panel plan may have asked already)
+        if (int rc = check_cols_sorted(p, d_flag_sorted, st)) return rc;
     if (!p.cols_sorted) return 0;  // stored order inside a row must be column order for the chunk walk
     std::vector<uint32_t> rorder;
     if (f.want_similarity) {

@@ -824,6 +824,51 @@ def test_unsorted_columns_inside_rows(rng):
         _lib.set_tunable("panel_bytes", old[1])
 
 
+@pytest.mark.parametrize("dt", ["INT32", "FLT32"])
+def test_a_created_groups_sweep_plan_is_the_one_the_rules_predict(rng, dt):
+    """group_plan and group_info of a created group against tests/sweep_plan_ref.py, the sweep's rules restated in numpy (the same helper the CPU test of
+    sweep_plan.hpp compares with), and the product against the CPU loop.  512 x 4096 in 2 panels of 2048 columns: a few entries in most rows, empty rows,
+    row 40 with 1500 entries inside panel 0 (more than 16 x 64: heavy, 24 segment tasks of 64), row 300 with 200 entries across both panels (100 a panel:
+    cooperative items above panel_coop = 64).  The same matrix with one row's columns stored out of order gets ONE panel"""
+    import sweep_plan_ref
+
+    npdt = NP_DTYPES[dt]
+    n, ncols, h = 512, 4096, 64
+    lengths = rng.integers(1, 7, size=n)
+    lengths[rng.choice(n, size=40, replace=False)] = 0
+    lengths[[40, 300]] = [1500, 200]
+    rows = [np.sort(rng.choice(ncols, size=k, replace=False)) for k in lengths]
+    rows[40] = np.sort(rng.choice(2048, size=1500, replace=False))
+    rows[300] = np.concatenate([np.sort(rng.choice(2048, size=100, replace=False)), 2048 + np.sort(rng.choice(2048, size=100, replace=False))])
+    rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    col = np.concatenate(rows).astype(np.int32)
+    shuffled = col.copy()
+    shuffled[rowptr[300]:rowptr[301]] = shuffled[rowptr[300]:rowptr[301]][::-1]
+    x = driver_features(rng, ncols, h, npdt)
+    knobs = dict(panel_mode=1, panel_bytes=128 * 2048, long_row_threshold=64, long_segment=64, panel_coop=64)
+    old = {k: _lib.set_tunable(k, v) for k, v in dict(knobs, lds_mode=0).items()}
+    try:
+        for cols, panels in ((col, 2), (shuffled, 1)):
+            want = sweep_plan_ref.plan(rowptr, cols, ncols, es=x.itemsize, h_hint=h, **knobs)
+            assert want["n_panels"] == panels and want["heavy"] == [40] and len(want["segment_tasks"]) == 3 * 24
+            assert want["panel_coop"] == ([1, 1] if panels == 2 else [1])
+            hd = _lib.group_create(_lib.CSR, CODE[dt], [_ptr(rowptr)], [_ptr(cols)], None, [n], [ncols], [len(cols)], [1], [h], h)
+            try:
+                plan, info = _lib.group_plan(hd), _lib.group_info(hd)
+                out = np.full((n, h), 77, dtype=npdt)
+                _lib.spmm_run_group(hd, [_ptr(x)], _ptr(out))
+            finally:
+                _lib.group_free(hd)
+            got = {k: plan[k] for k in ("n_panels", "panel_cols", "n_items", "col16", "n_coop_items", "n_segment_tasks")}
+            assert got == dict(n_panels=want["n_panels"], panel_cols=want["panel_cols"], n_items=want["n_items"], col16=want["col16"],
+                               n_coop_items=sum(want["panel_coop"]), n_segment_tasks=len(want["segment_tasks"]) // 3), (panels, got)
+            assert (info["n_panels"], info["n_items"]) == (want["n_panels"], want["n_items"])
+            assert np.array_equal(out, oracle.spmm_csr(rowptr, cols, None, x)), panels
+    finally:
+        for k, v in old.items():
+            _lib.set_tunable(k, v)
+
+
 @pytest.mark.parametrize("dt", ALL_DTYPES)
 def test_lds_staged_spmv_kernel(rng, dt):
     """k_spmv_lds (a column panel of X staged in a workgroup's LDS): rows of X of 1..4 elements, several panels with more than
